@@ -1,7 +1,16 @@
 """Benchmark: unlabeled images/sec of the FixMatch ViT-S/16 SSL step (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--dump-outputs DIR] [--full]
   (N>1: launched by torch.distributed.run, one rank per GPU, RCCL over xGMI)
+
+A plain run sets up, runs W warm-up steps, times K steps, writes its outputs (--dump-outputs) and prints
+one JSON line: metric / value / unit / higher_is_better / dtype / ms_per_step and what derives from the
+same K steps.  --full adds everything listed under "Reported beside it" (each takes launches, steps or a
+CPU run of its own) and, at N > 1, `weak_scaling` and the other all-reduce form.
+--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy (float32): the step's
+returned scalars, pseudo labels and mask, and a fixed seeded sample (DUMP_SAMPLE indices, seed 0) of the
+gradient, the updated weights and the EMA weights.  Inputs and initial weights are seeded, so two builds
+run with the same arguments are comparable array for array.
 
 Workload F1 (BASELINE configs[1]; configs[2] at N > 1): FixMatch, ViT-Small/16, global batch B=64
 labeled + mu*B = 448 unlabeled weak/strong pairs, 224x224x3, 23 classes, bf16 MFMA compute with
@@ -14,10 +23,10 @@ Scaling (north_star / SURVEY.md §8(e)): "strong" (default) shards the global ba
 exchange.  One step = weak forward + train forward/backward + fused losses + grad all-reduce +
 Adam/EMA sweep (code/fixmatch.py:91-131) -- nothing skipped.  Eager launches (--graph on replays
 the forward/backward as one captured hipGraph, FixMatch.use_graph: measured slower here).  At N > 1
-with strong scaling the line also carries `weak_scaling`: the same step timed with a full batch per
+with strong scaling the --full line also carries `weak_scaling`: the same step timed with a full batch per
 rank (configs[2] as DDP would run it).
 
-Reported beside it:
+Reported beside it (--full):
   roofline      the dominant kernel (the most GPU time per step: rocprofv3, profiles/r04e_summary.md) = a
                 transformer block's four weight-gradient GEMMs as ONE split-K launch (es_gemm_tn_big_grouped:
                 gemm_tn_big_grouped_kernel + its reduce), timed live by events the kernels stamp themselves
@@ -79,6 +88,36 @@ def synth_images(n, size, gen, device):
     m = torch.tensor(MEAN, device=device).view(1, 3, 1, 1)
     s = torch.tensor(STD, device=device).view(1, 3, 1, 1)
     return x.sub_(m).div_(s)
+
+
+DUMP_SAMPLE = 4_000_000  # indices kept of each flat state array: 3 arrays x 16 MB
+DUMP_MAX_BYTES = 64 * 10**6  # of everything one --dump-outputs writes (dump_outputs refuses more)
+
+
+def dump_outputs(path, out, tr):
+    """--dump-outputs: what the step that just ran handed its caller, as path/<name>.npy in float32 -- every
+    tensor of the dict `out` it returned, and the state it updated in place: the flat gradient, the weights and
+    the EMA weights of trainer `tr`.  A flat array longer than DUMP_SAMPLE is sampled at DUMP_SAMPLE indices
+    drawn once from torch.Generator seed 0 (with replacement): the same indices in every run of every build.
+    Call it before any further step: pseudo labels and mask live in buffers the next step overwrites."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    ema = getattr(getattr(tr, "ema_model", None), "ema", None)
+    for name, t in (("grad", getattr(tr.model, "flat_grad", None)), ("weights", getattr(tr.model, "flat", None)),
+                    ("ema_weights", getattr(ema, "flat", None))):
+        if torch.is_tensor(t):
+            arrays[name] = t
+    torch.cuda.synchronize()
+    total = sum(4 * min(t.numel(), DUMP_SAMPLE) for t in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {len(arrays)} arrays, {total} bytes as float32, over {DUMP_MAX_BYTES}")
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
 
 
 def host_cpus():
@@ -393,6 +432,8 @@ def run_secondary(args):
     if world > 1:
         torch.distributed.all_reduce(elapsed, op=torch.distributed.ReduceOp.MAX)
     T = elapsed.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, tr)
     host = None
     if args.host_input and args.workload in ("c1", "s1"):
         # C1 / S1 fed by the native host input path: TransformCoMatch's weak / strong_0 / strong_1 views
@@ -494,7 +535,14 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="global labeled batch B (strong) / per-GPU B (weak)")
     ap.add_argument("--mu", type=int, default=7)
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the headline: the dominant kernel's roofline (live "
+                         "and isolated), mfma_util, the CPU baseline, and at N > 1 weak scaling and the other "
+                         "all-reduce form; a plain run times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned and a seeded sample of the state it updated "
+                         "as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=16, help="cpu_baseline labeled batch B (64 = the F1 batch)")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--cpu-warmup", type=int, default=1)
@@ -593,7 +641,8 @@ def main():
         batch = tr.static_batch()  # the graph's own input buffers already hold this batch: no copy per step
     eng = model.engine()
     probe = {"label": "fc1_wgrad", "events": []}
-    live = not graph  # HIP events bracket eager launches only
+    full = args.full
+    live = full and not graph  # --full: HIP events bracket eager launches only
     if live:
         eng.probe = probe
     torch.cuda.synchronize()
@@ -610,27 +659,30 @@ def main():
         torch.distributed.all_reduce(elapsed, op=torch.distributed.ReduceOp.MAX)
     T = elapsed.item()
     loss = out["loss"].item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, tr)
 
-    # untimed steps after the timed region: the probed launch with the second stream off ("isolated"),
-    # and, when the timed steps replayed a graph, the same launch co-scheduled as in the step
-    use_graph, tr.use_graph = tr.use_graph, False
-    if not live:
-        eng.probe = probe
+    if full:
+        # untimed steps after the timed region: the probed launch with the second stream off ("isolated"),
+        # and, when the timed steps replayed a graph, the same launch co-scheduled as in the step
+        use_graph, tr.use_graph = tr.use_graph, False
+        if not live:
+            eng.probe = probe
+            for _ in range(2):
+                tr.step(batch)
+            torch.cuda.synchronize()
+        ov = (eng.overlap, eng.overlap_fwd)
+        eng.overlap = eng.overlap_fwd = False
+        iso = {"label": "fc1_wgrad", "events": []}
+        eng.probe = iso
         for _ in range(2):
             tr.step(batch)
         torch.cuda.synchronize()
-    ov = (eng.overlap, eng.overlap_fwd)
-    eng.overlap = eng.overlap_fwd = False
-    iso = {"label": "fc1_wgrad", "events": []}
-    eng.probe = iso
-    for _ in range(2):
-        tr.step(batch)
-    torch.cuda.synchronize()
-    eng.probe = None
-    eng.overlap, eng.overlap_fwd = ov
-    tr.use_graph = use_graph
+        eng.probe = None
+        eng.overlap, eng.overlap_fwd = ov
+        tr.use_graph = use_graph
     weak = None
-    if world > 1 and args.scaling == "strong":
+    if full and world > 1 and args.scaling == "strong":
         # configs[2] as the reference would run it under DDP: every rank a full B, mu batch (weak
         # scaling), timed the same way; reported beside the strong-scaling value (not the headline)
         xw, yw = make(args.batch, 224, g, dev), torch.randint(0, 23, (args.batch,), generator=g, device=dev)
@@ -652,7 +704,7 @@ def main():
                 "note": "same step with every rank on a full B=64, mu=7 batch (DDP weak scaling)"}
         del xw, yw, bw
     ar_overlap = None
-    if world > 1:
+    if full and world > 1:
         # the same step with the OTHER all-reduce form (the headline runs the form --allreduce chose: with
         # `auto` the faster of the per-block buckets overlapped with the reverse pass -- FixMatch.
         # overlap_allreduce / dist.GradBuckets -- and one all-reduce after it), so one multi-GPU run measures both
@@ -674,23 +726,59 @@ def main():
                       "note": "same step and batch with the other all-reduce form (per-block buckets overlapped "
                               "with the backward vs one all-reduce after it)"}
     host_input = host_input_run(tr, B, MU, args.steps, dev) if args.host_input else None
-    iso_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in iso["events"]) / len(iso["events"])
-    iso_tflops = (sum(f for _, _, f in iso["events"]) / (sum(e0.elapsed_time(e1) for e0, e1, _ in iso["events"]) / 1e3)
-                  / 1e12)
-    grouped = probe.get("kernel")  # the small-shard backward: the weight gradients as grouped launches
-    layer = probe.get("layer_kernel")  # a block's weight gradients as one split-K launch (Engine.LAYER_WGRAD)
-    ev_ms = [e0.elapsed_time(e1) for e0, e1, _ in probe["events"]]
-    mean_ms = sum(ev_ms) / len(ev_ms)
-    flop = sum(f for _, _, f in probe["events"]) / len(ev_ms)  # per launch (uniform at the fc1 site)
-    tflops = sum(f for _, _, f in probe["events"]) / (sum(ev_ms) / 1e3) / 1e12
-    M_tok = B * (1 + MU) * 197
-    if layer:
-        share = Engine.LAYER_TN_SHARE if ov[0] else 1.0
-    else:
-        share = (Engine.TN_SHARE if (ov[0] and not grouped and Engine.TN_SHARE < 1.0 and M_tok >= 16384) else 1.0)
-    traffic, traffic_src = (None, None) if grouped else pmc_traffic("es_gemm_tn_big_grouped" if layer else "gemm_tn")
-    lib = __import__("endossl._lib", fromlist=["load"]).load()
-    tn_ws = lib.es_gemm_tn_workspace(1536, 384, 0)
+    roofline = None
+    if full:
+        iso_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in iso["events"]) / len(iso["events"])
+        iso_tflops = (sum(f for _, _, f in iso["events"])
+                      / (sum(e0.elapsed_time(e1) for e0, e1, _ in iso["events"]) / 1e3) / 1e12)
+        grouped = probe.get("kernel")  # the small-shard backward: the weight gradients as grouped launches
+        layer = probe.get("layer_kernel")  # a block's weight gradients as one split-K launch (Engine.LAYER_WGRAD)
+        ev_ms = [e0.elapsed_time(e1) for e0, e1, _ in probe["events"]]
+        mean_ms = sum(ev_ms) / len(ev_ms)
+        flop = sum(f for _, _, f in probe["events"]) / len(ev_ms)  # per launch (uniform at the fc1 site)
+        tflops = sum(f for _, _, f in probe["events"]) / (sum(ev_ms) / 1e3) / 1e12
+        M_tok = B * (1 + MU) * 197
+        if layer:
+            share = Engine.LAYER_TN_SHARE if ov[0] else 1.0
+        else:
+            share = (Engine.TN_SHARE if (ov[0] and not grouped and Engine.TN_SHARE < 1.0 and M_tok >= 16384) else 1.0)
+        traffic, traffic_src = ((None, None) if grouped else
+                                pmc_traffic("es_gemm_tn_big_grouped" if layer else "gemm_tn"))
+        lib = __import__("endossl._lib", fromlist=["load"]).load()
+        tn_ws = lib.es_gemm_tn_workspace(1536, 384, 0)
+        roofline = {"kernel": (layer + " (bf16 operands, fp32 split-K slabs; rocprofv3: "
+                               "gemm_tn_big_grouped_kernel + splitk_reduce_grouped_kernel)" if layer else
+                               f"es_gemm_tn (weight gradient, fc1 site: out[1536, 384] = dY^T X over M={M_tok} "
+                               "train tokens, bf16 operands, fp32 split-K slabs + reduction, fused bias "
+                               "gradient); rocprofv3: gemm_tn_big_kernel + splitk_reduce_kernel"
+                               if not grouped else
+                               f"{grouped}: every weight gradient of the backward over M={M_tok} train tokens "
+                               "(Engine.GROUP_WGRAD, small shard), one launch per 4 layers, bf16 operands, "
+                               "whole-axis 128x128 tiles, fused bias gradients; rocprofv3: "
+                               "gemm_tn_grouped_kernel"),
+                    "bound": "mfma", "achieved": round(tflops, 1), "peak": round(PEAK_BF16_TFLOPS, 1),
+                    "unit": "TFLOP/s", "frac": round(tflops / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
+                    "traffic_source": (traffic_src + " (a separate rocprofv3 --pmc pass over this bench, "
+                                       "not measured in this run)") if traffic_src else None,
+                    "algorithmic_flop": flop, "mean_launch_ms": round(mean_ms, 4), "launches": len(ev_ms),
+                    "algorithmic_bytes": probe.get("layer_bytes"),
+                    "timed": ("live in the timed steps" if live else "2 untimed eager steps after the timed "
+                                                                     "(graph-replayed) steps")
+                             + ("; by events the kernel dispatches stamp themselves (hipExtLaunchKernelGGL: "
+                                "from the grouped kernel's start to the reduce launch's end, the span a "
+                                "rocprofv3 kernel trace shows, not the stream position of an event record)"
+                                if layer else ""),
+                    "streams": 2 if ov[0] else 1, "tn_workspace_floats": int(tn_ws),
+                    "cu_share": share,
+                    "frac_of_share": round(tflops / (PEAK_BF16_TFLOPS * share), 4),
+                    "share_note": ("the live launch is sized to this share of the CUs (Engine.TN_SHARE: "
+                                   "the rest run the data-gradient chain beside it); frac is against the "
+                                   "whole chip's peak, frac_of_share against the granted CUs' peak"),
+                    "isolated": {"mean_launch_ms": round(iso_ms, 4),
+                                 "achieved": round(iso_tflops, 1),
+                                 "frac": round(iso_tflops / PEAK_BF16_TFLOPS, 4),
+                                 "note": "same launch with the engine's second HIP stream off (2 untimed "
+                                         "steps): the live figure shares the CUs with the data-gradient chain"}}
 
     if rank == 0:
         ms = T / args.steps * 1e3
@@ -717,41 +805,10 @@ def main():
                                                            if Engine.PRUNE_LAST else 0.0))
                                          * glob_unl / 448.0, 3),
             "final_loss": round(loss, 6),
-            "roofline": {"kernel": (layer + " (bf16 operands, fp32 split-K slabs; rocprofv3: "
-                                    "gemm_tn_big_grouped_kernel + splitk_reduce_grouped_kernel)" if layer else
-                                    f"es_gemm_tn (weight gradient, fc1 site: out[1536, 384] = dY^T X over M={M_tok} "
-                                    "train tokens, bf16 operands, fp32 split-K slabs + reduction, fused bias "
-                                    "gradient); rocprofv3: gemm_tn_big_kernel + splitk_reduce_kernel"
-                                    if not grouped else
-                                    f"{grouped}: every weight gradient of the backward over M={M_tok} train tokens "
-                                    "(Engine.GROUP_WGRAD, small shard), one launch per 4 layers, bf16 operands, "
-                                    "whole-axis 128x128 tiles, fused bias gradients; rocprofv3: "
-                                    "gemm_tn_grouped_kernel"),
-                         "bound": "mfma", "achieved": round(tflops, 1), "peak": round(PEAK_BF16_TFLOPS, 1),
-                         "unit": "TFLOP/s", "frac": round(tflops / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
-                         "traffic_source": (traffic_src + " (a separate rocprofv3 --pmc pass over this bench, "
-                                            "not measured in this run)") if traffic_src else None,
-                         "algorithmic_flop": flop, "mean_launch_ms": round(mean_ms, 4), "launches": len(ev_ms),
-                         "algorithmic_bytes": probe.get("layer_bytes"),
-                         "timed": ("live in the timed steps" if live else "2 untimed eager steps after the timed "
-                                                                          "(graph-replayed) steps")
-                                  + ("; by events the kernel dispatches stamp themselves (hipExtLaunchKernelGGL: "
-                                     "from the grouped kernel's start to the reduce launch's end, the span a "
-                                     "rocprofv3 kernel trace shows, not the stream position of an event record)"
-                                     if layer else ""),
-                         "streams": 2 if ov[0] else 1, "tn_workspace_floats": int(tn_ws),
-                         "cu_share": share,
-                         "frac_of_share": round(tflops / (PEAK_BF16_TFLOPS * share), 4),
-                         "share_note": ("the live launch is sized to this share of the CUs (Engine.TN_SHARE: "
-                                        "the rest run the data-gradient chain beside it); frac is against the "
-                                        "whole chip's peak, frac_of_share against the granted CUs' peak"),
-                         "isolated": {"mean_launch_ms": round(iso_ms, 4),
-                                      "achieved": round(iso_tflops, 1),
-                                      "frac": round(iso_tflops / PEAK_BF16_TFLOPS, 4),
-                                      "note": "same launch with the engine's second HIP stream off (2 untimed "
-                                              "steps): the live figure shares the CUs with the data-gradient chain"}},
         }
-        sc, sc_src = step_counters()
+        if roofline is not None:
+            res["roofline"] = roofline
+        sc, sc_src = step_counters() if full else (None, None)
         if sc is not None and world == 1:
             busy = sc["step"]["mfma_busy_simd_cycles"]
             same = sc.get("lib_sha256") is not None and sc.get("lib_sha256") == lib_sha256()
@@ -770,16 +827,17 @@ def main():
                         "the .md"}
         if weak is not None:
             res["weak_scaling"] = weak
-        if ar_overlap is not None:
+        if world > 1:
             res["allreduce_form"] = "overlapped per-block buckets" if tr.overlap_allreduce else "one after the backward"
-            res["allreduce_other_form"] = ar_overlap
+            if ar_overlap is not None:
+                res["allreduce_other_form"] = ar_overlap
             if ar_probe is not None:
                 res["allreduce_choice"] = {"probe_ms_per_step": ar_probe,
                                            "note": "--allreduce auto: both forms timed for 3 untimed steps before the "
                                                    "timed region (max over ranks); the faster one is the headline"}
         if host_input is not None:
             res["host_input"] = host_input
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(B=args.cpu_batch, steps=args.cpu_steps, warmup=args.cpu_warmup)
         print(json.dumps(res), flush=True)
     dist.barrier()

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Same-box A/B/... of library builds, interleaved R rounds of `bench.py --no-cpu-baseline $BARGS`.
+# Same-box A/B/... of library builds, interleaved R rounds of `bench.py --full --no-cpu-baseline $BARGS`.
 #   LIBS="A=path/libA.so B=path/libB.so ..." (default: A = csrc/build/ab/libA.so, made by scripts/build_ab.sh
 #   <ref>, and B = the tree's own library)
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; OUT="$GRAFT_REPO_ROOT/gpurun_out"; export TMPDIR=/tmp
@@ -9,7 +9,7 @@ for r in $(seq ${R:-3}); do
   line="round $r"
   for kv in $LIBS; do
     k=${kv%%=*}; lib=${kv#*=}
-    ENDOSSL_LIB=$lib timeout -k 10 ${LIM:-240} python -u bench.py --no-cpu-baseline ${BARGS} > "$OUT/abl_${k}$r.log" 2>&1 || exit 1
+    ENDOSSL_LIB=$lib timeout -k 10 ${LIM:-240} python -u bench.py --full --no-cpu-baseline ${BARGS} > "$OUT/abl_${k}$r.log" 2>&1 || exit 1
     line="$line  $k $(ms $OUT/abl_${k}$r.log)"
   done
   echo "$line"

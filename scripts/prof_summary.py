@@ -85,11 +85,12 @@ if os.path.exists(tr):
         # blocks 10..1
         tspan = [sp for v in per_step.values() for _, sp, _ in sorted(v)[1:]]
         tkern = [kk for v in per_step.values() for _, _, kk in sorted(v)[1:]]
-        rl = line["roofline"]
+        rl = line.get("roofline")  # a `bench.py --full` log carries it; a plain run's does not
         site += (f" In the {k} timed steps of the same process, blocks 10..1 ({len(tspan)} launches): kernel start to "
-                 f"reduce end {sum(tspan) / len(tspan):.1f} us (kernel alone {sum(tkern) / len(tkern):.1f} us) against "
-                 f"the bench line's `mean_launch_ms` {rl['mean_launch_ms'] * 1e3:.1f} us over its {rl.get('launches')} "
-                 f"launches: {rl['mean_launch_ms'] * 1e3 / (sum(tspan) / len(tspan)):.3f}x.")
+                 f"reduce end {sum(tspan) / len(tspan):.1f} us (kernel alone {sum(tkern) / len(tkern):.1f} us)")
+        site += (f" against the bench line's `mean_launch_ms` {rl['mean_launch_ms'] * 1e3:.1f} us over its "
+                 f"{rl.get('launches')} launches: {rl['mean_launch_ms'] * 1e3 / (sum(tspan) / len(tspan)):.3f}x."
+                 if rl else " (a plain bench run: no `mean_launch_ms` to set beside it).")
     lines += ["", "The bench's roofline site (a block's four weight-gradient GEMMs, fc2 / fc1 / proj / qkv over "
               "M = 100,864 tokens) is the `gemm_tn_big_grouped_kernel` launch of 96 workgroups (24 tiles of 384 x 192 "
               "x 4 splits, 3/8 of the CUs, 11 per step: blocks 11..1, block 11's on its K / V slice alone) plus its `splitk_reduce_grouped_kernel`; the first block's "

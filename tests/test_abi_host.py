@@ -99,14 +99,52 @@ def test_config_defaults_fill_missing_keys(tmp_path):
     assert c.MODEL.MARGIN == "None"  # PyYAML parses `None` as a string
 
 
-def test_reference_configs_parse():
-    from endossl.utils import get_config
-    cdir = "/root/reference/code/configs"
-    if not os.path.isdir(cdir):
-        pytest.skip("reference configs only in the build container")
-    for f in sorted(os.listdir(cdir)):
-        c = get_config(os.path.join(cdir, f))
+_CONFIG_FILES = {
+    # a supervised run: no SSL keys at all, no PRE_TRAIN_RESUME / IS_FREEZE / SAVE_CP
+    "supervised.yaml": ("DATA:\n IMG_SIZE: 224\n BATCH_SIZE: 32\n NUM_WORKERS: 4\n INPUT_NAME: 'image'\n"
+                        "MODEL:\n NAME: 'resnet18'\n NUM_CLASSES: 23\n PRE_TRAIN: True\n MARGIN: None\n"
+                        "TRAIN:\n IS_SSL: False\n EPOCHS: 30\n BASE_LR: 0.0005\n BETAS: [0.9, 0.999]\n"
+                        " SCH_NAME: 'cosine'\n USE_EMA: False\n"),
+    # a FixMatch run: flow-style and trailing blanks, MU / THRES / LAMBDA_U given, EMA_DECAY and IS_FREEZE left out
+    "fixmatch.yaml": ("DATA: {BATCH_SIZE: 16, MU: 5, IMG_SIZE: 64}\n"
+                      "MODEL:\n NAME: 'vit_tiny_test'  \n NUM_CLASSES: 6\n TYPE_SEMI: 'FixMatch'\n"
+                      "TRAIN:\n IS_SSL: True\n THRES: 0.7 \n LAMBDA_U: 2\n EVAL_STEP: 8\n WARMUP_EPOCHS: 5  \n"),
+    # a CoMatch run on the Conformer with a checkpoint to resume from; no DATA section at all
+    "comatch.yaml": ("MODEL:\n NAME: 'conformer'\n TYPE_SEMI: 'CoMatch'\n LOW_DIM: 128\n"
+                     " PRE_TRAIN_RESUME: 'runs/last.pth'\n IS_TRIPLET: False\n"
+                     "TRAIN:\n IS_FREEZE: True\n LAMBDA_C: 4\n SAVE_CP: 'runs/'\n EMA_DECAY: 0.99\n"),
+}
+
+
+def test_config_files_parse_and_fill_omissions(tmp_path):
+    """get_config over config files of the three kinds of run: what a file gives is kept as YAML types it,
+    and every key the trainers dereference is there afterwards, from DEFAULTS where the file leaves it out
+    (files that omit PRE_TRAIN_RESUME, IS_FREEZE or SAVE_CP must not crash the trainer at its first lookup)."""
+    from endossl.utils import DEFAULTS, get_config
+    cfgs = {}
+    for name, text in _CONFIG_FILES.items():
+        (tmp_path / name).write_text(text)
+        c = cfgs[name] = get_config(str(tmp_path / name))
+        for sec, vals in DEFAULTS.items():
+            for k in vals:
+                assert k in c[sec], (name, sec, k)
         assert "BATCH_SIZE" in c.DATA and "EMA_DECAY" in c.TRAIN
+    sup, fm, cm = (cfgs[n] for n in ("supervised.yaml", "fixmatch.yaml", "comatch.yaml"))
+    assert sup.DATA.BATCH_SIZE == 32 and sup.DATA.NUM_WORKERS == 4 and sup.DATA.INPUT_NAME == "image"
+    assert sup.MODEL.MARGIN == "None" and sup.MODEL.PRE_TRAIN is True and sup.TRAIN.BETAS == [0.9, 0.999]
+    assert sup.TRAIN.IS_SSL is False and sup.TRAIN.USE_EMA is False and sup.TRAIN.SCH_NAME == "cosine"
+    assert sup.MODEL.PRE_TRAIN_RESUME == "None" and sup.TRAIN.IS_FREEZE is False and sup.TRAIN.SAVE_CP == "."
+    assert (fm.DATA.BATCH_SIZE, fm.DATA.MU, fm.DATA.IMG_SIZE) == (16, 5, 64) and fm.DATA.TARGET_NAME == "target"
+    assert fm.MODEL.NAME == "vit_tiny_test" and fm.MODEL.NUM_CLASSES == 6 and fm.MODEL.LOW_DIM == 64
+    assert fm.TRAIN.THRES == 0.7 and fm.TRAIN.LAMBDA_U == 2 and fm.TRAIN.EVAL_STEP == 8 and fm.TRAIN.WARMUP_EPOCHS == 5
+    assert fm.TRAIN.EMA_DECAY == 0.999 and fm.TRAIN.IS_FREEZE is False and fm.TRAIN.T == 1.0
+    assert cm.DATA == DEFAULTS["DATA"]  # the whole section from the defaults
+    assert cm.MODEL.TYPE_SEMI == "CoMatch" and cm.MODEL.LOW_DIM == 128 and cm.MODEL.PRE_TRAIN_RESUME == "runs/last.pth"
+    assert cm.TRAIN.IS_FREEZE is True and cm.TRAIN.LAMBDA_C == 4 and cm.TRAIN.SAVE_CP == "runs/"
+    assert cm.TRAIN.EMA_DECAY == 0.99 and cm.TRAIN.THRES == 0.95
+    # without fill_defaults the file's own keys alone
+    raw = get_config(str(tmp_path / "fixmatch.yaml"), fill_defaults=False)
+    assert set(raw.DATA) == {"BATCH_SIZE", "MU", "IMG_SIZE"} and "EMA_DECAY" not in raw.TRAIN
 
 
 def test_step_scheduler_and_warmup():
