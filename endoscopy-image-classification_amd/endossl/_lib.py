@@ -158,6 +158,8 @@ SIGNATURES = {
     "es_ce_weight_sum": (I, [V, V, I, I, V, V]),
     "es_ce_weighted_fwd_bwd_global": (I, [V, I, V, V, V, I, I, F, V, I, V, V]),
     "es_adam_ema_step": (I, [V, V, V, V, V, L, F, F, F, F, F, F, F, F, V]),
+    "es_adamw_ema_step": (I, [V, V, V, V, V, V, L, F, F, F, F, F, F, F, F, F, F, F, F, F, V]),
+    "es_sgd_ema_step": (I, [V, V, V, V, V, L, F, F, F, F, F, I, F, F, F, V]),
     "es_ema_entry_size": (I, []),
     "es_ema_update_multi": (I, [V, V, I, F, F, V]),
     "es_pack_entry_size": (I, []),

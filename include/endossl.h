@@ -532,6 +532,23 @@ int es_ce_weighted_fwd_bwd_global(const float* logits, int ldl, const int64_t* t
 int es_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2,
                      float eps, float neg_step, float bc2_sqrt, float decay, float one_minus_decay,
                      float grad_scale, hipStream_t stream);
+/* AdamW and SGD (momentum, Nesterov) sweeps with per-param-group lr / weight decay (code/optimizer.py:43-49),
+ * fused with the same EMA blend (ema nullable).  `cls` is the class map: one byte per 64 consecutive floats of
+ * the flat buffer (n / 64 bytes; every parameter starts at a multiple of 64 floats), 0 = not trained (frozen
+ * parameter or alignment padding: p, g and the moments are neither updated nor written, only the EMA blend
+ * runs), 1 = param group 0, 2 = param group 1.  n % 64 == 0 and n < 2^38 (else ES_BAD_SHAPE); p, g, cls and the
+ * moments non-null, every float buffer 16-byte aligned and cls 4-byte aligned (else ES_BAD_ARG).
+ * AdamW: p *= decay_mul_c [= (float)(1 - lr_c wd_c)], then the Adam update with neg_step_c = -lr_c / (1 - beta1^t);
+ * one_minus_beta{1,2} = (float)(1 - beta) rounded from double, as torch passes them (within 1e-6 of the fp32
+ * 1 - beta, else ES_BAD_ARG).
+ * SGD: d = g grad_scale + wd_c p; buf = buf momentum + d; p += neg_lr_c (nesterov ? d + momentum buf : buf). */
+int es_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema, const uint8_t* cls, long n,
+                      float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                      float bc2_sqrt, float neg_step0, float neg_step1, float decay_mul0, float decay_mul1,
+                      float decay, float one_minus_decay, float grad_scale, hipStream_t stream);
+int es_sgd_ema_step(float* p, const float* g, float* buf, float* ema, const uint8_t* cls, long n, float momentum,
+                    float neg_lr0, float neg_lr1, float wd0, float wd1, int nesterov, float decay,
+                    float one_minus_decay, float grad_scale, hipStream_t stream);
 int es_ema_entry_size(void);
 int es_ema_update_multi(const void* entries, const void* chunks, int nchunks, float decay, float one_minus_decay,
                         hipStream_t stream);
