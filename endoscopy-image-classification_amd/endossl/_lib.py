@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("ENDOSSL_LIB", os.path.join(_HERE, "lib", "libendossl_
 V, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_size_t
 U64 = ctypes.c_ulonglong
 
-# name -> (restype, argtypes).  Mirrors include/endossl.h one-to-one (tests/test_abi.py checks it).
+# name -> (restype, argtypes).  Mirrors include/endossl.h one-to-one (tests/test_abi_host.py checks it).
 SIGNATURES = {
     "es_abi_version": (I, []),
     "es_gemm_nt": (I, [I, V, I, V, I, V, V, I, V, V, I, I, I, I, I, V]),

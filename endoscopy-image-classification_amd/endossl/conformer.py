@@ -26,6 +26,7 @@ MI355X-first layout:
     launch overwrites its slice), which the native Adam reads.  PyTorch provides the autograd
     graph, device memory and streams only.
 """
+import contextlib
 import ctypes
 import math
 import os
@@ -34,12 +35,10 @@ from copy import deepcopy
 import torch
 import torch.nn as nn
 
-from . import _lib, dist
+from . import _lib, block, dist
 from ._lib import call, ptr
 from .vit import IMAGENET_MEAN, IMAGENET_STD
 
-EPI_BF16, EPI_GELU, EPI_F32_RESID, EPI_DGELU, EPI_F32 = 0, 1, 2, 3, 4
-EPI_GELU_ACT, EPI_GELU_D, EPI_MULAUX = 6, 7, 8
 BN_EPS_BLOCK, BN_EPS_STEM, LN_EPS, LN_EPS_TRANS_NORM = 1e-6, 1e-5, 1e-6, 1e-5
 BN_MOMENTUM = 0.1
 
@@ -282,30 +281,9 @@ CONF_TN_SHARE = 0.5
 CONF_TN_GROUPED = False
 
 
-def _wgrad_grouped(m, probs, M, target, k):
-    """One es_gemm_tn_big_grouped launch (+ its reduce) on the current stream over probs = [(dy, N1, x, N2,
-    weight name, bias name)]: out / bias gradients overwritten (as es_gemm_tn with accumulate 0)."""
-    from .vit import _TNProblem
-    lib = _lib.load()
-    n = len(probs)
-    tab = (_TNProblem * n)()
-    for e, (dy, N1, x, N2, wname, bname) in zip(tab, probs):
-        e.dy, e.x, e.out = ptr(dy), ptr(x), ptr(m.gview(wname))
-        e.bias_out = ptr(m.gview(bname)) if bname else None
-        e.M, e.N1, e.N2, e.ld1, e.ld2 = M, N1, N2, N1, N2
-    need = lib.es_gemm_tn_big_grouped_workspace(ctypes.byref(tab), n, target)
-    ws = m.bwd_scratch(f"tn_grouped_ws/{k}", (max(int(need), 1),), torch.float32)
-    raw = ctypes.create_string_buffer(lib.es_gemm_tn_big_grouped_table_bytes(n))
-    dims = (ctypes.c_int * 3)()
-    rc = lib.es_gemm_tn_big_grouped_prepare(ctypes.byref(tab), n, target, ptr(ws), ws.numel(), raw, dims)
-    if rc != 0:
-        raise _lib.EndosslLibraryError(f"es_gemm_tn_big_grouped_prepare: status {rc}")
-    call("es_gemm_tn_big_grouped", raw, n, dims, _s())
-
-
-def _tn_splits(M, N1, N2):
-    """0: es_gemm_tn sizes the split-K for the kernel it picks (as the ViT engine, Engine._tn_splits)."""
-    return 0
+def _chain(m):
+    """The transformer blocks' launch chain over the model's parameters and weight images (the engine's defaults)."""
+    return block.Chain(call, m.pview, m.gview, m.wb, m.wt, m.cfg.heads, LN_EPS)
 
 
 # CNN-branch conv operands in bf16 (csrc/conv_bf16.hip: v_mfma_f32_16x16x32_bf16, fp32 maps and
@@ -466,7 +444,7 @@ class _ConvFn(torch.autograd.Function):
             _queue_join(main, side)
             x.record_stream(side)
             dy.record_stream(side)
-        with torch.cuda.stream(side) if side is not None else _nullctx():
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             ws = torch.empty(wsn, device=dy.device)
             call(dwfn, xp, xm.N, xm.H, xm.W, xm.C, xm.sn, xm.sh, xm.sw, xm.sc, ptr(dy),
                  Ho * Wo * Cout, Wo * Cout, Cout, Cout, k, k, s, p, splits, ptr(ws), ptr(m.gview(wname)), 0,
@@ -493,14 +471,6 @@ class _ConvFn(torch.autograd.Function):
         elif CAPTURE is not None:  # no input gradient (the stem reads the images): dy for the weight gradient
             CAPTURE("bwd", wname, dy, None, None)
         return dx, None, None, None, None, None, None, None, None, None, None, None, None
-
-
-class _nullctx:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *a):
-        return False
 
 
 def conv(m, x, xmap, wname, bname, Cout, k, s=1, p=0, anchor=None, stats=False, sink=None, out_dtype=None):
@@ -666,7 +636,7 @@ class _BNConvFn(torch.autograd.Function):
             _queue_join(main, side)
             for t in (x, dy, mean, rstd):
                 t.record_stream(side)
-        with torch.cuda.stream(side) if side is not None else _nullctx():
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             ws = torch.empty(lib.es_conv2d_bwd_weight_bf16_workspace(M, Cout, C, k, k, 0), device=dy.device)
             call("es_conv2d_bwd_weight_bf16_bnin_ex", ptr(x), N, H, W, C, H * W * C, W * C, C, 1, ptr(dy),
                  Ho * Wo * Cout, Wo * Cout, Cout, Cout, k, k, s, p, 0, ptr(ws), ptr(m.gview(wname)), 0,
@@ -872,7 +842,6 @@ class _BlockFn(torch.autograd.Function):
         Mp = xt.shape[0]
         n = m.cur_n
         M = n * T
-        s = _s()
         dev = xt.device
         b16 = torch.bfloat16
         # rows [M, Mp) of the weight-gradient GEMM operands (h1, o, h2, act) must read as zero; every
@@ -890,24 +859,11 @@ class _BlockFn(torch.autograd.Function):
         # gradients (the weak pass) the activation alone
         grad = ctx.needs_input_grad[0]
         gd, act = (e(Mp, Hd, dt=b16) if grad else None), zp(Mp, Hd, dt=b16)
-        pv, wb = m.pview, m.wb
-        call("es_layernorm_fwd", ptr(xt), D, ptr(pv(pre + "norm1.weight")), ptr(pv(pre + "norm1.bias")), ptr(h1), D,
-             ptr(mean1), ptr(rstd1), M, D, LN_EPS, s)
-        call("es_gemm_nt", EPI_BF16, ptr(h1), D, ptr(wb[pre + "attn.qkv.weight"]), D, ptr(pv(pre + "attn.qkv.bias")),
-             ptr(qkv), 3 * D, None, None, 0, M, 3 * D, D, 0, s)
-        call("es_attn_fwd", ptr(qkv), 3 * D, ptr(o), D, ptr(lse), n, T, H, 64 ** -0.5, s)
-        call("es_gemm_nt", EPI_F32_RESID, ptr(o), D, ptr(wb[pre + "attn.proj.weight"]), D,
-             ptr(pv(pre + "attn.proj.bias")), ptr(xmid), D, None, ptr(xt), D, M, D, D, 0, s)
-        call("es_layernorm_fwd", ptr(xmid), D, ptr(pv(pre + "norm2.weight")), ptr(pv(pre + "norm2.bias")), ptr(h2), D,
-             ptr(mean2), ptr(rstd2), M, D, LN_EPS, s)
-        if grad:
-            call("es_gemm_nt", EPI_GELU_D, ptr(h2), D, ptr(wb[pre + "mlp.fc1.weight"]), D,
-                 ptr(pv(pre + "mlp.fc1.bias")), ptr(gd), Hd, ptr(act), None, 0, M, Hd, D, 0, s)
-        else:
-            call("es_gemm_nt", EPI_GELU_ACT, ptr(h2), D, ptr(wb[pre + "mlp.fc1.weight"]), D,
-                 ptr(pv(pre + "mlp.fc1.bias")), ptr(act), Hd, None, None, 0, M, Hd, D, 0, s)
-        call("es_gemm_nt", EPI_F32_RESID, ptr(act), Hd, ptr(wb[pre + "mlp.fc2.weight"]), Hd,
-             ptr(pv(pre + "mlp.fc2.bias")), ptr(out), D, None, ptr(xmid), D, M, D, Hd, 0, s)
+        ch = _chain(m)
+        R = block.Rows(n, T, H, x=xt, h1=h1, mean1=mean1, rstd1=rstd1, qkv=qkv, o=o, lse=lse, xmid=xmid, h2=h2,
+                       mean2=mean2, rstd2=rstd2, pre=gd, act=act, out=out)
+        ch.attn_fwd(pre, R)
+        ch.mlp_fwd(pre, R, grad)
         ctx.save_for_backward(xt, h1, mean1, rstd1, qkv, o, lse, xmid, h2, mean2, rstd2, gd, act)
         ctx.m, ctx.pre, ctx.n = m, pre, n
         if BLOCK_CAPTURE is not None and grad:
@@ -923,7 +879,6 @@ class _BlockFn(torch.autograd.Function):
         D, Hd, T, H = cfg.dim, cfg.hidden, cfg.T, cfg.heads
         Mp = xt.shape[0]
         M = n * T
-        s = _s()
         dev = xt.device
         b16 = torch.bfloat16
         # layer-internal scratch, reused by every other block's backward: allocated zeroed once, so the
@@ -940,9 +895,13 @@ class _BlockFn(torch.autograd.Function):
             main.wait_event(m._blk_events.pop(k))
         lib = _lib.load()
         dout = dout.contiguous()
-        dxb = z("dxb", Mp, D, dt=b16)
-        call("es_cast_f32_bf16", ptr(dout), ptr(dxb), Mp * D, s)
-        wt, pv, gv = m.wt, m.pview, m.gview
+        # d(LN output) (dh, dh2) in bf16, as the ViT engine (Engine.DH_BF16); dx is made before the LN1 backward
+        R = block.Rows(n, T, H, dxb=z("dxb", Mp, D, dt=b16), pre=gd, act=act, dpre=z("dpre", Mp, Hd, dt=b16),
+                       dh=z("dh", Mp, D, dt=b16), h2=h2, xmid=xmid, mean2=mean2, rstd2=rstd2, dres=dout,
+                       dxm=z("dxm", Mp, D), dxmb=z("dxmb", Mp, D, dt=b16), do=z("do", Mp, D, dt=b16), o=o, qkv=qkv,
+                       lse=lse, delta=z("delta", n * H * T), dqkv=z("dqkv", Mp, 3 * D, dt=b16),
+                       dh1=z("dh2", Mp, D, dt=b16), h1=h1, x=xt, mean1=mean1, rstd1=rstd1, dx=None, dxb_next=None)
+        block.cast_f32_bf16(call, dout, R.dxb, Mp * D)
         ws_ln = torch.empty(2 * 1024 * D, device=dev)
 
         # the grouped launch's shapes: every N1 a multiple of 384, every N2 of 192; rows [M, Mp) of every
@@ -950,65 +909,42 @@ class _BlockFn(torch.autograd.Function):
         grouped = (CONF_TN_GROUPED and xt.is_cuda and D % 384 == 0 and Hd % 384 == 0 and Mp >= _rup(M, 64))
         probs = []
 
-        def wgrad(dy, N1, x, N2, wname, bname):
+        def wgrad(dy, N1, x, N2, Mw, out, bias_out, label=None):
             if grouped:
-                probs.append((dy, N1, x, N2, wname, bname))
+                probs.append((dy, N1, x, N2, Mw, out, bias_out, N1, N2))
                 return
-            sp = _tn_splits(M, N1, N2)
+            sp = 0  # es_gemm_tn sizes the split-K for the kernel it picks
             if side is not None and CONF_TN_SHARE < 1.0 and M >= 65536 and N1 % 384 == 0 and N2 % 192 == 0:
                 # beside the branch streams: the 384 x 192 tile on a share of the CUs (as Engine.TN_SHARE)
                 ncu = torch.cuda.get_device_properties(dev).multi_processor_count
                 sp = max(1, int(ncu * CONF_TN_SHARE) // ((N1 // 384) * (N2 // 192)))
-            if side is not None:
-                side.wait_stream(main)
-            with torch.cuda.stream(side) if side is not None else _nullctx():
+            with block.on_stream(side, main):
                 ws = torch.empty(lib.es_gemm_tn_workspace(N1, N2, sp), device=dev)
-                call("es_gemm_tn", ptr(dy), N1, ptr(x), N2, M, N1, N2, sp, ptr(ws), ptr(gv(wname)), 0,
-                     ptr(gv(bname)), _s())
+                call("es_gemm_tn", ptr(dy), N1, ptr(x), N2, M, N1, N2, sp, ptr(ws), ptr(out), 0, ptr(bias_out), _s())
 
-        dpre = z("dpre", Mp, Hd, dt=b16)
-        call("es_gemm_nt", EPI_MULAUX, ptr(dxb), D, ptr(wt[pre + "mlp.fc2.weight"]), D, None, ptr(dpre), Hd, None,
-             ptr(gd), Hd, M, Hd, D, 0, s)
-        wgrad(dxb, D, act, Hd, pre + "mlp.fc2.weight", pre + "mlp.fc2.bias")
-        dh = z("dh", Mp, D, dt=b16)  # d(LN output) in bf16, as the ViT engine (Engine.DH_BF16)
-        call("es_gemm_nt", EPI_BF16, ptr(dpre), Hd, ptr(wt[pre + "mlp.fc1.weight"]), Hd, None, ptr(dh), D, None,
-             None, 0, M, D, Hd, 0, s)
-        wgrad(dpre, Hd, h2, D, pre + "mlp.fc1.weight", pre + "mlp.fc1.bias")
-        dxm, dxmb = z("dxm", Mp, D), z("dxmb", Mp, D, dt=b16)
-        call("es_layernorm_bwd_b16", ptr(dh), D, ptr(xmid), D, ptr(mean2), ptr(rstd2), ptr(pv(pre + "norm2.weight")),
-             ptr(dout), D, ptr(dxm), D, ptr(dxmb), D, ptr(gv(pre + "norm2.weight")), ptr(gv(pre + "norm2.bias")),
-             ptr(ws_ln), 1024, M, D, 0, s)
-        do = z("do", Mp, D, dt=b16)
-        call("es_gemm_nt", EPI_BF16, ptr(dxmb), D, ptr(wt[pre + "attn.proj.weight"]), D, None, ptr(do), D, None,
-             None, 0, M, D, D, 0, s)
-        wgrad(dxmb, D, o, D, pre + "attn.proj.weight", pre + "attn.proj.bias")
-        dqkv = z("dqkv", Mp, 3 * D, dt=b16)
-        delta = z("delta", n * H * T)
-        call("es_attn_bwd", ptr(qkv), 3 * D, ptr(o), D, ptr(lse), ptr(delta), ptr(do), D, ptr(dqkv), 3 * D, n, T, H,
-             64 ** -0.5, s)
-        dh2 = z("dh2", Mp, D, dt=b16)
-        call("es_gemm_nt", EPI_BF16, ptr(dqkv), 3 * D, ptr(wt[pre + "attn.qkv.weight"]), 3 * D, None, ptr(dh2), D,
-             None, None, 0, M, D, 3 * D, 0, s)
-        wgrad(dqkv, 3 * D, h1, D, pre + "attn.qkv.weight", pre + "attn.qkv.bias")
-        if probs:
-            ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-            target = max(1, int(ncu * CONF_TN_SHARE)) if side is not None else ncu
-            if side is not None:
-                side.wait_stream(main)
-            with torch.cuda.stream(side) if side is not None else _nullctx():
-                _wgrad_grouped(m, probs, M, target, k)
-        dx = _zero_pad(torch.empty(Mp, D, device=dev), M)  # returned to autograd: fresh
-        call("es_layernorm_bwd_b16", ptr(dh2), D, ptr(xt), D, ptr(mean1), ptr(rstd1), ptr(pv(pre + "norm1.weight")),
-             ptr(dxm), D, ptr(dx), D, None, 0, ptr(gv(pre + "norm1.weight")), ptr(gv(pre + "norm1.bias")),
-             ptr(ws_ln), 1024, M, D, 0, s)
+        def ln_bwd(dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, Ml, lddx=None):
+            block.layernorm_bwd(call, dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, ws_ln, 1024, Ml, D, 0)
+
+        def before_ln1():
+            if probs:  # the block's four weight gradients as one grouped launch (CONF_TN_GROUPED)
+                ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+                target = max(1, int(ncu * CONF_TN_SHARE)) if side is not None else ncu
+                with block.on_stream(side, main):
+                    block.tn_big_grouped(probs, target, lambda need: m.bwd_scratch(
+                        f"tn_grouped_ws/{k}", (max(int(need), 1),), torch.float32))
+            R.dx = _zero_pad(torch.empty(Mp, D, device=dev), M)  # returned to autograd: fresh
+
+        ch = _chain(m)
+        ch.mlp_bwd(pre, R, ln_bwd, wgrad)
+        ch.attn_bwd(pre, R, ln_bwd, wgrad, before_ln1)
         if BLOCK_CAPTURE is not None:
-            BLOCK_CAPTURE("bwd", pre, n, dout, dxb, dpre, dh, dxm, dxmb, do, dqkv, dh2, dx)
+            BLOCK_CAPTURE("bwd", pre, n, dout, R.dxb, R.dpre, R.dh, R.dxm, R.dxmb, R.do, R.dqkv, R.dh1, R.dx)
         if side is not None:
             for t in (act, h2, o, h1):  # saved activations the side stream still reads
                 t.record_stream(side)
             m._blk_events[k] = side.record_event()
             _queue_join(main, side)
-        return dx, None, None
+        return R.dx, None, None
 
 
 class _ConvHeadFn(torch.autograd.Function):

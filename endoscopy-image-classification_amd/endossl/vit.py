@@ -24,10 +24,11 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, block
 from ._lib import call, ptr
+from .block import (EPI_BF16, EPI_DGELU, EPI_F32, EPI_F32_RESID, EPI_GELU, EPI_GELU_ACT,  # noqa: F401 -- re-exported
+                    EPI_GELU_D, EPI_MULAUX, EPI_PATCH, Rows, _TNProblem)
 
-EPI_BF16, EPI_GELU, EPI_F32_RESID, EPI_DGELU, EPI_F32, EPI_PATCH, EPI_GELU_ACT, EPI_GELU_D, EPI_MULAUX = range(9)
 # LayerNorm backward workgroups (grid-stride over row pairs; per-workgroup dgamma / dbeta partials)
 LN_BWD_BLOCKS = 1024
 # HIP priority of the second stream (weak forward, overlapped weight gradients) for steps of at least
@@ -220,14 +221,6 @@ class _Grads:
         self.dxm_cls = z(Mp, D)
 
 
-class _TNProblem(ctypes.Structure):
-    """es_tn_problem (include/endossl.h): one GEMM of a grouped weight-gradient launch."""
-    _fields_ = [("dy", ctypes.c_void_p), ("x", ctypes.c_void_p), ("out", ctypes.c_void_p),
-                ("bias_out", ctypes.c_void_p), ("M", ctypes.c_int), ("N1", ctypes.c_int), ("N2", ctypes.c_int),
-                ("ld1", ctypes.c_int), ("ld2", ctypes.c_int), ("mchunk", ctypes.c_int), ("tile0", ctypes.c_int),
-                ("pad", ctypes.c_int)]
-
-
 class Engine:
     """Explicit forward / backward of the ViT over C-ABI kernels.  One per (model, device)."""
 
@@ -324,7 +317,7 @@ class Engine:
         self._lnp_next = 0
         self._side = None
         self._ncu = None
-        self._lane_state = {}
+        self._lane_state, self._gtab = {}, {}
         self._grad_b = None
         self.overlap = self.OVERLAP
         self.overlap_fwd = self.OVERLAP_FWD
@@ -366,18 +359,24 @@ class Engine:
             name = self.PARITY_NAMES.get(name, name)
         return call(name, *args)
 
-    def _gemm(self, label, *args):
-        """es_gemm_nt, optionally bracketed by HIP events on the launch stream (bench roofline)."""
+    def _bracket(self, label, flop, launch):
+        """launch(), between HIP events when `label` is the probed site (bench roofline: the probe returned)."""
         pr = self.probe
-        if pr is not None and pr["label"] == label:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            self._call("es_gemm_nt", *args)
-            e1.record()
-            M, N, K = args[11], args[12], args[13]
-            pr["events"].append((e0, e1, 2.0 * M * N * K))
-        else:
-            self._call("es_gemm_nt", *args)
+        if pr is None or pr["label"] != label:
+            launch()
+            return None
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+        pr["events"].append((e0, e1, flop))
+        return pr
+
+    def _chain(self, flat, grad=None):
+        """The block chain (block.Chain) over this engine's parameters, weight images and kernel choices."""
+        return block.Chain(self._call, lambda name: self.view(flat, name), lambda name: self.view(grad, name),
+                           self.wb, self.wt, self.cfg.heads, self.cfg.eps, gelu_d=self.GELU_D, dh_bf16=self.DH_BF16,
+                           bracket=self._bracket)
 
     # -------------------------------------------------------------- helpers
     def view(self, flat, name):
@@ -444,7 +443,7 @@ class Engine:
         s = _lib.stream()
         n = sum(int(t.shape[0]) for t in images_list)
         A = self.acts(n, train)
-        D, Hd, T, H = cfg.dim, cfg.hidden, cfg.T, cfg.heads
+        D, T, H = cfg.dim, cfg.T, cfg.heads
         K0 = 3 * cfg.patch * cfg.patch
         row = 0
         for t in images_list:
@@ -461,61 +460,30 @@ class Engine:
             row += int(t.shape[0])
         x0 = A.x[0]
         pos = self.view(flat, "pos_embed")
-        self._call("es_gemm_nt", EPI_PATCH, ptr(A.patches), K0, ptr(self.wb["patch_embed.proj.weight"]), K0,
-             ptr(self.view(flat, "patch_embed.proj.bias")), ptr(x0), D, None, ptr(pos), D, n * cfg.np, D, K0,
-             cfg.np, s)
+        block.gemm_nt(self._call, EPI_PATCH, A.patches, self.wb["patch_embed.proj.weight"],
+                      self.view(flat, "patch_embed.proj.bias"), x0, n * cfg.np, D, K0, aux=pos, ldaux=D, npatch=cfg.np)
         self._call("es_cls_init", ptr(x0), D, ptr(self.view(flat, "cls_token")), ptr(pos), n, T, D, s)
         M = A.M
         prune = self._prune()
+        ch = self._chain(flat)
+        fused = self.RESID_LN and D == 384 and self.precision == "bf16" and M >= self.RESID_LN_MIN_M
         for i in range(cfg.depth):
             b = f"blocks.{i}."
             li = i if train else 0
             xin = A.x[i] if train else A.x[i & 1]
             xout = A.x[i + 1] if train else A.x[(i + 1) & 1]
-            xmid, h1, h2 = A.xmid[li], A.h1[li], A.h2[li]
-            self._call("es_layernorm_fwd", ptr(xin), D, ptr(self.view(flat, b + "norm1.weight")),
-                 ptr(self.view(flat, b + "norm1.bias")), ptr(h1), D, ptr(A.mean1[li]), ptr(A.rstd1[li]), M, D,
-                 cfg.eps, s)
-            if prune and self.PRUNE_Q and i == cfg.depth - 1:
-                # K and V for every token; Q for the CLS rows only, written to their rows of qkv
-                wq, bq = self.wb[b + "attn.qkv.weight"], self.view(flat, b + "attn.qkv.bias")
-                self._call("es_gemm_nt", EPI_BF16, ptr(h1), D, ptr(wq[D:]), D, ptr(bq[D:]), ptr(A.qkv[li][:, D:]), 3 * D,
-                     None, None, 0, M, 2 * D, D, 0, s)
-                A.c_h1[:n].copy_(h1[:M].view(n, T, D)[:, 0])
-                self._call("es_gemm_nt", EPI_BF16, ptr(A.c_h1), D, ptr(wq[:D]), D, ptr(bq[:D]), ptr(A.qkv[li]), T * 3 * D,
-                     None, None, 0, n, D, D, 0, s)
-            else:
-                self._call("es_gemm_nt", EPI_BF16, ptr(h1), D, ptr(self.wb[b + "attn.qkv.weight"]), D,
-                     ptr(self.view(flat, b + "attn.qkv.bias")), ptr(A.qkv[li]), 3 * D, None, None, 0, M, 3 * D, D, 0,
-                     s)
+            R = Rows(n, T, H, x=xin, h1=A.h1[li], mean1=A.mean1[li], rstd1=A.rstd1[li], qkv=A.qkv[li], o=A.o[li],
+                     lse=A.lse[li], xmid=A.xmid[li], h2=A.h2[li], mean2=A.mean2[li], rstd2=A.rstd2[li],
+                     pre=A.pre[li] if train else None, act=A.act[li], out=xout)
             if prune and i == cfg.depth - 1:
-                self._last_block_cls_fwd(flat, A, b, li, xin, n, train, s)
+                Rc = self._cls_rows(A, n, xin)
+                ch.attn_fwd(b, R, cls=Rc, split_q=self.PRUNE_Q)
+                ch.mlp_fwd(b, Rc, train)
                 if self.capture is not None:
                     self.capture("fwd_cls", train, i, xin[:M], A.c_xout[:n])
                 break
-            self._call("es_attn_fwd", ptr(A.qkv[li]), 3 * D, ptr(A.o[li]), D, ptr(A.lse[li]), n, T, H, 64 ** -0.5, s)
-            if self.RESID_LN and D == 384 and self.precision == "bf16" and M >= self.RESID_LN_MIN_M:
-                self._call("es_gemm_nt_resid_ln", ptr(A.o[li]), D, ptr(self.wb[b + "attn.proj.weight"]), D,
-                     ptr(self.view(flat, b + "attn.proj.bias")), ptr(xmid), D, ptr(xin), D,
-                     ptr(self.view(flat, b + "norm2.weight")), ptr(self.view(flat, b + "norm2.bias")), ptr(h2), D,
-                     ptr(A.mean2[li]), ptr(A.rstd2[li]), M, D, D, cfg.eps, s)
-            else:
-                self._call("es_gemm_nt", EPI_F32_RESID, ptr(A.o[li]), D, ptr(self.wb[b + "attn.proj.weight"]), D,
-                     ptr(self.view(flat, b + "attn.proj.bias")), ptr(xmid), D, None, ptr(xin), D, M, D, D, 0, s)
-                self._call("es_layernorm_fwd", ptr(xmid), D, ptr(self.view(flat, b + "norm2.weight")),
-                     ptr(self.view(flat, b + "norm2.bias")), ptr(h2), D, ptr(A.mean2[li]), ptr(A.rstd2[li]), M, D,
-                     cfg.eps, s)
-            if train:
-                self._gemm("fc1_fwd", EPI_GELU_D if self.GELU_D else EPI_GELU, ptr(h2), D,
-                           ptr(self.wb[b + "mlp.fc1.weight"]), D,
-                           ptr(self.view(flat, b + "mlp.fc1.bias")), ptr(A.pre[li]), Hd, ptr(A.act[li]), None, 0, M,
-                           Hd, D, 0, s)
-            else:
-                self._gemm("fc1_fwd_weak", EPI_GELU_ACT, ptr(h2), D, ptr(self.wb[b + "mlp.fc1.weight"]), D,
-                           ptr(self.view(flat, b + "mlp.fc1.bias")), ptr(A.act[li]), Hd, None, None, 0, M, Hd, D, 0,
-                           s)
-            self._call("es_gemm_nt", EPI_F32_RESID, ptr(A.act[li]), Hd, ptr(self.wb[b + "mlp.fc2.weight"]), Hd,
-                 ptr(self.view(flat, b + "mlp.fc2.bias")), ptr(xout), D, None, ptr(xmid), D, M, D, Hd, 0, s)
+            ch.attn_fwd(b, R)
+            ch.mlp_fwd(b, R, train, fused=fused, label="fc1_fwd" if train else "fc1_fwd_weak")
             if self.capture is not None:
                 self.capture("fwd", train, i, xin[:M], xout[:M])
         xl = A.x[cfg.depth] if train else A.x[cfg.depth & 1]
@@ -536,27 +504,17 @@ class Engine:
         the two-lane backward runs every row."""
         return self.PRUNE_LAST
 
-    def _last_block_cls_fwd(self, flat, A, b, li, xin, n, train, s):
-        """The last block after its qkv GEMM, on the CLS rows only (PRUNE_LAST): CLS-query attention
-        over all keys, then projection (+ the residual read from the CLS rows of xin in place), LN2
-        and the MLP on n compact rows -> A.c_xout."""
-        cfg = self.cfg
-        D, Hd, T, H = cfg.dim, cfg.hidden, cfg.T, cfg.heads
-        fv = lambda name: ptr(self.view(flat, name))  # noqa: E731
-        self._call("es_attn_cls_fwd", ptr(A.qkv[li]), 3 * D, ptr(A.c_o), D, ptr(A.c_lse), n, T, H, 64 ** -0.5, s)
-        self._call("es_gemm_nt", EPI_F32_RESID, ptr(A.c_o), D, ptr(self.wb[b + "attn.proj.weight"]), D,
-             fv(b + "attn.proj.bias"), ptr(A.c_xmid), D, None, ptr(xin), T * D, n, D, D, 0, s)
-        self._call("es_layernorm_fwd", ptr(A.c_xmid), D, fv(b + "norm2.weight"), fv(b + "norm2.bias"), ptr(A.c_h2), D,
-             ptr(A.c_mean2), ptr(A.c_rstd2), n, D, cfg.eps, s)
-        if train:
-            self._call("es_gemm_nt", EPI_GELU_D if self.GELU_D else EPI_GELU, ptr(A.c_h2), D,
-                 ptr(self.wb[b + "mlp.fc1.weight"]), D, fv(b + "mlp.fc1.bias"), ptr(A.c_pre), Hd, ptr(A.c_act), None,
-                 0, n, Hd, D, 0, s)
-        else:
-            self._call("es_gemm_nt", EPI_GELU_ACT, ptr(A.c_h2), D, ptr(self.wb[b + "mlp.fc1.weight"]), D,
-                 fv(b + "mlp.fc1.bias"), ptr(A.c_act), Hd, None, None, 0, n, Hd, D, 0, s)
-        self._call("es_gemm_nt", EPI_F32_RESID, ptr(A.c_act), Hd, ptr(self.wb[b + "mlp.fc2.weight"]), Hd,
-             fv(b + "mlp.fc2.bias"), ptr(A.c_xout), D, None, ptr(A.c_xmid), D, n, D, Hd, 0, s)
+    def _cls_rows(self, A, n, xin=None, G=None):
+        """The pruned last block's compact CLS row set (PRUNE_LAST): CLS-query attention over all keys, then
+        projection (+ the residual read from the CLS rows of xin in place), LN2 and the MLP on n compact rows ->
+        A.c_xout.  G: the reverse pass's, d(xmid) landing on the CLS rows of the token image G.dxm_cls (else zero)."""
+        T, D = self.cfg.T, self.cfg.dim
+        R = Rows(n, 1, self.cfg.heads, ldx=T * D, lddxm=T * D, x=xin, h1=A.c_h1, o=A.c_o, lse=A.c_lse, xmid=A.c_xmid,
+                 h2=A.c_h2, mean2=A.c_mean2, rstd2=A.c_rstd2, pre=A.c_pre, act=A.c_act, out=A.c_xout)
+        if G is not None:
+            R.dxb, R.dpre, R.dh, R.dres, R.dxmb, R.do = G.c_dxb, G.c_dpre, G.c_dh, G.c_dx, G.c_dxmb, G.c_do
+            R.dxm = G.dxm_cls
+        return R
 
     # -------------------------------------------------------------- backward
     def _tn_splits(self, M, N1, N2):
@@ -590,40 +548,27 @@ class Engine:
         # pin (es_set_tn_variant, ENDOSSL_TN_VARIANT) still wins inside the library
         variant = 7 if splits and self._tn_shared(M, N1, N2) else -1
         args = (ptr(dy), ld1 or N1, ptr(x), ld2 or N2, M, N1, N2, splits, ptr(ws), ptr(out), 0, ptr(bias_out))
-        self._wgrad_launch(args, variant, M, N1, N2, label)
-
-    def _wgrad_launch(self, args, variant, M, N1, N2, label):
         if self.precision == "fp32":  # parity mode: the fp32 twin (no kernel variants)
             fn, args = "es_gemm_tn", args + (_lib.stream(),)
         else:
             fn, args = "es_gemm_tn_ex", args + (variant, _lib.stream())
-        pr = self.probe
-        if pr is not None and label is not None and pr["label"] == label:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            self._call(fn, *args)
-            e1.record()
-            pr["events"].append((e0, e1, 2.0 * M * N1 * N2))
-        else:
-            self._call(fn, *args)
+        self._bracket(label, 2.0 * M * N1 * N2, lambda: self._call(fn, *args))
 
     def _ln_bwd(self, dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, M, lane=0, lddx=None, accumulate=0,
                 defer=None):
         """defer (a list): the parameter gradients' partials stay in a workspace of their own, recorded in
         `defer` for one es_ln_param_grads_multi launch later (Engine.DEFER_LN_GRADS)."""
         D = self.cfg.dim
-        fn = "es_layernorm_bwd_b16" if dy.dtype == torch.bfloat16 else "es_layernorm_bwd"  # (_f32 in parity mode)
         grid = _lib.load().es_layernorm_bwd_grid(LN_BWD_BLOCKS, M)
         if defer is not None and grid >= 64:  # (one multi-reduce launch takes one column-width class: grid >= 64)
             ws = self.ln_part_workspace(self._lnp_next)  # never reused within a reverse pass (the side stream
             self._lnp_next += 1                           # may reduce a flushed one after the chain moved on)
-            self._call(fn, ptr(dy), D, ptr(x), D, ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), D, ptr(dx), lddx or D,
-                       ptr(dxb), D, None, None, ptr(ws), LN_BWD_BLOCKS, M, D, 0, _lib.stream())
+            block.layernorm_bwd(self._call, dy, x, mean, rstd, gamma, dres, dx, dxb, None, None, ws, LN_BWD_BLOCKS, M,
+                                D, 0, lddx)
             defer.append((ws, dgamma, dbeta, grid, accumulate))
             return
-        ws = self.ln_workspace(lane)
-        self._call(fn, ptr(dy), D, ptr(x), D, ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), D, ptr(dx), lddx or D,
-             ptr(dxb), D, ptr(dgamma), ptr(dbeta), ptr(ws), LN_BWD_BLOCKS, M, D, accumulate, _lib.stream())
+        block.layernorm_bwd(self._call, dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, self.ln_workspace(lane),
+                            LN_BWD_BLOCKS, M, D, accumulate, lddx)
 
     def ln_part_workspace(self, k):
         """The k-th deferred LayerNorm backward's partials of a reverse pass (Engine.DEFER_LN_GRADS)."""
@@ -662,7 +607,6 @@ class Engine:
         (dist.GradBuckets); ranges never handed over are the caller's to finish."""
         cfg = self.cfg
         s = _lib.stream()
-        EPI_DH = EPI_BF16 if self.DH_BF16 else EPI_F32  # noqa: N806
         top = dfts if cfg.head == "emb" else dlogits
         if top is None:
             raise ValueError("Engine.backward needs dlogits (cls head) or dfts (emb head)")
@@ -674,7 +618,7 @@ class Engine:
             self._grads[n] = (_Grads(cfg, n, self.device, self.op_dtype), _Grads(cfg, n, self.device, self.op_dtype))
         G = self._grads[n][0]
         GS = self._grads[n]
-        D, Hd, T, H, M = cfg.dim, cfg.hidden, cfg.T, cfg.heads, A.M
+        D, Hd, T, M = cfg.dim, cfg.hidden, cfg.T, A.M
         gv = lambda name: self.view(grad, name)  # noqa: E731
         fv = lambda name: self.view(flat, name)  # noqa: E731
         ov = self.overlap
@@ -711,11 +655,7 @@ class Engine:
                     and (ld1 or N1) % 8 == 0 and (ld2 or N2) % 8 == 0):
                 lp.append((dy, N1, x, N2, Mw, out, bias_out, ld1 or N1, ld2 or N2, label))
                 return
-            if not ov:
-                self._wgrad(dy, N1, x, N2, Mw, out, bias_out, ld1=ld1, ld2=ld2, label=label)
-                return
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
+            with block.on_stream(side, main):
                 self._wgrad(dy, N1, x, N2, Mw, out, bias_out, ld1=ld1, ld2=ld2, label=label)
 
         done = {}
@@ -725,20 +665,12 @@ class Engine:
             LayerNorm parameter gradients deferred so far)."""
             if not lp and not (layer_wg and lnd):
                 return
-            probs = list(lp)
-            lp.clear()
-
-            def run():
-                if probs:
-                    self._wgrad_layer(probs, i)
+            with block.on_stream(side, main):
+                if lp:
+                    self._wgrad_layer(lp, i)
+                    lp.clear()
                 if layer_wg and lnd:
                     self._ln_grads_flush(lnd)
-            if ov:
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    run()
-            else:
-                run()
 
         def block_done(i):
             if self.capture is not None:
@@ -747,20 +679,9 @@ class Engine:
                 # these layers' weight gradients as one grouped launch on the side stream (two lanes: a third
                 # stream after both), beside the rest of the data-gradient chain (their dY sets are never
                 # rewritten within the step)
-                if lanes:
-                    third.wait_stream(main)
-                    third.wait_stream(side)
-                    with torch.cuda.stream(third):
-                        self._launch_grouped(problems, i)
-                elif ov:
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side):
-                        self._launch_grouped(problems, i)
-                        if lnd:
-                            self._ln_grads_flush(lnd)
-                else:
+                with block.on_stream(third, main, side) if lanes else block.on_stream(side, main):
                     self._launch_grouped(problems, i)
-                    if lnd:
+                    if lnd:  # (None with lanes)
                         self._ln_grads_flush(lnd)
                 problems.clear()
             if grad_ready is None:
@@ -795,96 +716,48 @@ class Engine:
         if self.capture is not None:
             self.capture("dtop", True, cfg.depth - 1, dtop[:n] if prune else G.dx[:M])
         if prune:
-            self._call("es_cast_f32_bf16", ptr(GL.c_dx), ptr(GL.c_dxb), n * D, s)
+            block.cast_f32_bf16(self._call, GL.c_dx, GL.c_dxb, n * D)
         else:
-            self._call("es_cast_f32_bf16", ptr(G.dx), ptr(GL.dxb), M * D, s)
+            block.cast_f32_bf16(self._call, G.dx, GL.dxb, M * D)
+        ch = self._chain(flat, grad)
+        ln_bwd = lambda *a, **kw: self._ln_bwd(*a, defer=lnd, **kw)  # noqa: E731
+        cap = block.nop  # test hook: each reverse-pass intermediate of a full-row block as the next op reads it
         for i in reversed(range(cfg.depth)):
             b = f"blocks.{i}."
             if grouped:
                 Gi, Gn = GS[i], GS[i - 1] if i > 0 else GS[cfg.depth]
             else:
                 Gi, Gn = GS[i % 2], GS[(i - 1) % 2]
-            if prune and i == cfg.depth - 1:
-                # ---- the last block on its CLS rows: MLP, LN2 and projection over n compact rows
-                self._call("es_gemm_nt", EPI_MULAUX if self.GELU_D else EPI_DGELU, ptr(Gi.c_dxb), D,
-                     ptr(self.wt[b + "mlp.fc2.weight"]), D, None, ptr(Gi.c_dpre), Hd, None, ptr(A.c_pre), Hd, n, Hd,
-                     D, 0, s)
-                wgrad_side(Gi.c_dxb, D, A.c_act, Hd, n, gv(b + "mlp.fc2.weight"), gv(b + "mlp.fc2.bias"))
-                self._call("es_gemm_nt", EPI_DH, ptr(Gi.c_dpre), Hd, ptr(self.wt[b + "mlp.fc1.weight"]), Hd, None,
-                     ptr(Gi.c_dh), D, None, None, 0, n, D, Hd, 0, s)
-                wgrad_side(Gi.c_dpre, Hd, A.c_h2, D, n, gv(b + "mlp.fc1.weight"), gv(b + "mlp.fc1.bias"))
-                # d(xmid) lands on the CLS rows of the full token image dxm_cls (zero elsewhere)
-                self._ln_bwd(Gi.c_dh, A.c_xmid, A.c_mean2, A.c_rstd2, fv(b + "norm2.weight"), Gi.c_dx, Gi.dxm_cls,
-                             Gi.c_dxmb, gv(b + "norm2.weight"), gv(b + "norm2.bias"), n, lddx=T * D, defer=lnd)
-                self._call("es_gemm_nt", EPI_BF16, ptr(Gi.c_dxmb), D, ptr(self.wt[b + "attn.proj.weight"]), D, None,
-                     ptr(Gi.c_do), D, None, None, 0, n, D, D, 0, s)
-                wgrad_side(Gi.c_dxmb, D, A.c_o, D, n, gv(b + "attn.proj.weight"), gv(b + "attn.proj.bias"))
-                self._call("es_attn_cls_bwd", ptr(A.qkv[i]), 3 * D, ptr(A.c_o), D, ptr(A.c_lse), ptr(Gi.c_do), D,
-                     ptr(Gi.dqkv), 3 * D, n, T, H, 64 ** -0.5, s)
-                self._call("es_gemm_nt", EPI_DH, ptr(Gi.dqkv), 3 * D, ptr(self.wt[b + "attn.qkv.weight"]), 3 * D, None,
-                     ptr(G.dh), D, None, None, 0, M, D, 3 * D, 0, s)
-                gw, gb = gv(b + "attn.qkv.weight"), gv(b + "attn.qkv.bias")
-                if self.PRUNE_Q and n % 32 == 0:
-                    # K / V weight gradients over every token; the Q part over the CLS rows, the only
-                    # rows with a nonzero dQ (strided views: rows img*T of dqkv and h1)
-                    wgrad_side(Gi.dqkv[:, D:], 2 * D, A.h1[i], D, M, gw[D * D:], gb[D:], ld1=3 * D)
-                    wgrad_side(Gi.dqkv, D, A.h1[i], D, n, gw[:D * D], gb[:D], ld1=T * 3 * D, ld2=T * D)
-                else:
-                    wgrad_side(Gi.dqkv, 3 * D, A.h1[i], D, M, gw, gb)
+            if self.capture is not None:
+                cap = lambda kind, *ts, i=i: self.capture(kind, True, i, *(t[:M] for t in ts))  # noqa: E731
+
+            def before_ln1(i=i):
                 flush_layer(i)
                 if ovw:
                     done[i] = side.record_event()
-                self._ln_bwd(G.dh, A.x[i], A.mean1[i], A.rstd1[i], fv(b + "norm1.weight"), Gi.dxm_cls, G.dx, Gn.dxb,
-                             gv(b + "norm1.weight"), gv(b + "norm1.bias"), M, defer=lnd)
-                block_done(i)
-                continue
-            if lanes:
+                    if i + 1 in done:  # set (i-1) % 2 was layer i+1's: its weight gradients must be done
+                        main.wait_event(done.pop(i + 1))
+            if lanes and not (prune and i == cfg.depth - 1):
                 if i == (cfg.depth - 2 if prune else cfg.depth - 1):
                     side.wait_stream(main)  # lane 1 starts from the last block's (or the head's) output gradient
-                self._lanes_block(flat, grad, A, G, Gi, Gn, i, n, nh, main, side)
+                self._lanes_block(ch, b, A, G, Gi, Gn, i, n, nh, main, side)
                 wgrad_side(Gi.dxb, D, A.act[i], Hd, M, gv(b + "mlp.fc2.weight"), gv(b + "mlp.fc2.bias"))
                 wgrad_side(Gi.dpre, Hd, A.h2[i], D, M, gv(b + "mlp.fc1.weight"), gv(b + "mlp.fc1.bias"))
                 wgrad_side(Gi.dxmb, D, A.o[i], D, M, gv(b + "attn.proj.weight"), gv(b + "attn.proj.bias"))
                 wgrad_side(Gi.dqkv, 3 * D, A.h1[i], D, M, gv(b + "attn.qkv.weight"), gv(b + "attn.qkv.bias"))
                 block_done(i)
                 continue
-            # ---- MLP:  x_{i+1} = xmid + fc2(gelu(fc1(LN2(xmid))))
-            cap = self.capture  # test hook: each reverse-pass intermediate as the next op reads it
-            if cap is not None:
-                cap("b_dxb", True, i, Gi.dxb[:M])
-            self._call("es_gemm_nt", EPI_MULAUX if self.GELU_D else EPI_DGELU, ptr(Gi.dxb), D,
-                 ptr(self.wt[b + "mlp.fc2.weight"]), D, None, ptr(Gi.dpre), Hd, None, ptr(A.pre[i]), Hd, M, Hd, D, 0, s)
-            wgrad_side(Gi.dxb, D, A.act[i], Hd, M, gv(b + "mlp.fc2.weight"), gv(b + "mlp.fc2.bias"))
-            self._call("es_gemm_nt", EPI_DH, ptr(Gi.dpre), Hd, ptr(self.wt[b + "mlp.fc1.weight"]), Hd, None, ptr(G.dh),
-                 D, None, None, 0, M, D, Hd, 0, s)
-            wgrad_side(Gi.dpre, Hd, A.h2[i], D, M, gv(b + "mlp.fc1.weight"), gv(b + "mlp.fc1.bias"), label="fc1_wgrad")
-            if cap is not None:
-                cap("b_dpre", True, i, Gi.dpre[:M])
-                cap("b_dh2", True, i, G.dh[:M])
-            self._ln_bwd(G.dh, A.xmid[i], A.mean2[i], A.rstd2[i], fv(b + "norm2.weight"), G.dx, G.dxm, Gi.dxmb,
-                         gv(b + "norm2.weight"), gv(b + "norm2.bias"), M, defer=lnd)
-            # ---- attention:  xmid = x_i + proj(attn(LN1(x_i)))
-            self._call("es_gemm_nt", EPI_BF16, ptr(Gi.dxmb), D, ptr(self.wt[b + "attn.proj.weight"]), D, None, ptr(G.do), D,
-                 None, None, 0, M, D, D, 0, s)
-            wgrad_side(Gi.dxmb, D, A.o[i], D, M, gv(b + "attn.proj.weight"), gv(b + "attn.proj.bias"))
-            if cap is not None:
-                cap("b_dxm", True, i, G.dxm[:M], Gi.dxmb[:M])
-                cap("b_do", True, i, G.do[:M])
-            self._call("es_attn_bwd", ptr(A.qkv[i]), 3 * D, ptr(A.o[i]), D, ptr(A.lse[i]), ptr(G.delta), ptr(G.do), D,
-                 ptr(Gi.dqkv), 3 * D, n, T, H, 64 ** -0.5, s)
-            self._call("es_gemm_nt", EPI_DH, ptr(Gi.dqkv), 3 * D, ptr(self.wt[b + "attn.qkv.weight"]), 3 * D, None,
-                 ptr(G.dh), D, None, None, 0, M, D, 3 * D, 0, s)
-            wgrad_side(Gi.dqkv, 3 * D, A.h1[i], D, M, gv(b + "attn.qkv.weight"), gv(b + "attn.qkv.bias"))
-            if cap is not None:
-                cap("b_dqkv", True, i, Gi.dqkv[:M])
-                cap("b_dh1", True, i, G.dh[:M])
-            flush_layer(i)
-            if ovw:
-                done[i] = side.record_event()
-                if i + 1 in done:  # set (i-1) % 2 was layer i+1's: its weight gradients must be done
-                    main.wait_event(done.pop(i + 1))
-            self._ln_bwd(G.dh, A.x[i], A.mean1[i], A.rstd1[i], fv(b + "norm1.weight"), G.dxm, G.dx, Gn.dxb,
-                         gv(b + "norm1.weight"), gv(b + "norm1.bias"), M, defer=lnd)
+            R = self._bwd_rows(A, G, Gi, Gn, i, n)
+            if prune and i == cfg.depth - 1:
+                # the last block on its CLS rows: MLP, LN2 and projection over n compact rows, then the CLS
+                # queries' attention backward into the full dqkv image; d(xmid) is Gi.dxm_cls
+                Rc, R.dxm = self._cls_rows(A, n, G=Gi), Gi.dxm_cls
+                ch.mlp_bwd(b, Rc, ln_bwd, wgrad_side)
+                ch.attn_bwd(b, R, ln_bwd, wgrad_side, before_ln1, cls=Rc, split_q=self.PRUNE_Q and n % 32 == 0)
+            else:
+                # MLP: x_{i+1} = xmid + fc2(gelu(fc1(LN2(xmid)))), then attention: xmid = x_i + proj(attn(LN1(x_i)))
+                ch.mlp_bwd(b, R, ln_bwd, wgrad_side, cap, label="fc1_wgrad")
+                ch.attn_bwd(b, R, ln_bwd, wgrad_side, before_ln1, cap)
             block_done(i)
         # ---- embedding: x_0 = [cls; patch_embed(img)] + pos
         K0 = 3 * cfg.patch * cfg.patch
@@ -905,50 +778,36 @@ class Engine:
             main.wait_stream(third)
         return grad
 
-    def _lanes_block(self, flat, grad, A, G, Gi, Gn, i, n, nh, main, side):
+    def _bwd_rows(self, A, G, Gi, Gn, i, n, i0=0):
+        """Block i's reverse-pass row set over images [i0, i0 + n): its dY images in Gi (the weight gradients'
+        inputs), the bf16 d(block input) in Gn (the next block's), everything else in G."""
+        return Rows(n, self.cfg.T, self.cfg.heads, i0, dxb=Gi.dxb, pre=A.pre[i], act=A.act[i], dpre=Gi.dpre, dh=G.dh,
+                    h2=A.h2[i], xmid=A.xmid[i], mean2=A.mean2[i], rstd2=A.rstd2[i], dres=G.dx, dxm=G.dxm, dxmb=Gi.dxmb,
+                    do=G.do, o=A.o[i], qkv=A.qkv[i], lse=A.lse[i], delta=G.delta, dqkv=Gi.dqkv, dh1=G.dh, h1=A.h1[i],
+                    x=A.x[i], mean1=A.mean1[i], rstd1=A.rstd1[i], dx=G.dx, dxb_next=Gn.dxb)
+
+    def _lanes_block(self, ch, b, A, G, Gi, Gn, i, n, nh, main, side):
         """Block i's data-gradient chain as two lanes (Engine.SHARD_LANES): images [0, nh) on the caller's
         stream, [nh, n) on the side stream, each on its rows of the same buffers (token rows are per image, the
         chain never mixes images).  The LayerNorm parameter gradients are the only sums over both halves: lane 1
         adds its share to lane 0's (accumulate), ordered by an event.  Lane 0 finished block i+1 on main, lane 1
         on side; the embedding backward waits for both."""
-        cfg = self.cfg
-        D, Hd, T, H = cfg.dim, cfg.hidden, cfg.T, cfg.heads
-        EPI_DH = EPI_BF16 if self.DH_BF16 else EPI_F32  # noqa: N806
-        b = f"blocks.{i}."
-        fv = lambda name: self.view(flat, name)  # noqa: E731
-        gv = lambda name: self.view(grad, name)  # noqa: E731
         ev = {}
         for ln, st in ((0, main), (1, side)):
             i0, nl = (0, nh) if ln == 0 else (nh, n - nh)
-            r0, Ml = i0 * T, nl * T
+            which = iter(("ln2", "ln1"))
+
+            def ln_bwd(*a, ln=ln, st=st, which=which, **kw):
+                k = next(which)
+                if ln == 1:
+                    st.wait_event(ev[k])
+                self._ln_bwd(*a, lane=ln, accumulate=ln, **kw)
+                if ln == 0:
+                    ev[k] = st.record_event()
             with torch.cuda.stream(st):
-                s = _lib.stream()
-                rp = lambda t, r0=r0: ptr(t[r0:])  # noqa: E731
-                self._call("es_gemm_nt", EPI_MULAUX if self.GELU_D else EPI_DGELU, rp(Gi.dxb), D,
-                           ptr(self.wt[b + "mlp.fc2.weight"]), D, None, rp(Gi.dpre), Hd, None, rp(A.pre[i]), Hd, Ml, Hd,
-                           D, 0, s)
-                self._call("es_gemm_nt", EPI_DH, rp(Gi.dpre), Hd, ptr(self.wt[b + "mlp.fc1.weight"]), Hd, None,
-                           rp(G.dh), D, None, None, 0, Ml, D, Hd, 0, s)
-                if ln == 1:
-                    st.wait_event(ev["ln2"])
-                self._ln_bwd(G.dh[r0:], A.xmid[i][r0:], A.mean2[i][r0:], A.rstd2[i][r0:], fv(b + "norm2.weight"),
-                             G.dx[r0:], G.dxm[r0:], Gi.dxmb[r0:], gv(b + "norm2.weight"), gv(b + "norm2.bias"), Ml,
-                             lane=ln, accumulate=ln)
-                if ln == 0:
-                    ev["ln2"] = st.record_event()
-                self._call("es_gemm_nt", EPI_BF16, rp(Gi.dxmb), D, ptr(self.wt[b + "attn.proj.weight"]), D, None,
-                           rp(G.do), D, None, None, 0, Ml, D, D, 0, s)
-                self._call("es_attn_bwd", rp(A.qkv[i]), 3 * D, rp(A.o[i]), D, ptr(A.lse[i][i0 * H * T:]),
-                           ptr(G.delta[i0 * H * T:]), rp(G.do), D, rp(Gi.dqkv), 3 * D, nl, T, H, 64 ** -0.5, s)
-                self._call("es_gemm_nt", EPI_DH, rp(Gi.dqkv), 3 * D, ptr(self.wt[b + "attn.qkv.weight"]), 3 * D, None,
-                           rp(G.dh), D, None, None, 0, Ml, D, 3 * D, 0, s)
-                if ln == 1:
-                    st.wait_event(ev["ln1"])
-                self._ln_bwd(G.dh[r0:], A.x[i][r0:], A.mean1[i][r0:], A.rstd1[i][r0:], fv(b + "norm1.weight"),
-                             G.dxm[r0:], G.dx[r0:], Gn.dxb[r0:], gv(b + "norm1.weight"), gv(b + "norm1.bias"), Ml,
-                             lane=ln, accumulate=ln)
-                if ln == 0:
-                    ev["ln1"] = st.record_event()
+                R = self._bwd_rows(A, G, Gi, Gn, i, nl, i0)
+                ch.mlp_bwd(b, R, ln_bwd)
+                ch.attn_bwd(b, R, ln_bwd)
 
     def _wgrad_layer(self, problems, layer):
         """One es_gemm_tn_big_grouped launch (+ its reduce) over a block's weight gradients, on the
@@ -956,25 +815,11 @@ class Engine:
         beside it; the first block's (the last launch of the backward: nothing left beside it) and the
         serial engine's to the whole chip.  The problem table travels in the kernel arguments (no
         host->device copy; capturable)."""
-        lib = _lib.load()
         if self._ncu is None:
             self._ncu = torch.cuda.get_device_properties(self.device).multi_processor_count
         share = self.LAYER_TN_SHARE if (self.overlap and layer > 0) else 1.0  # block 0 / the embedding: chip
         target = max(1, int(self._ncu * share))
-        n = len(problems)
-        tab = (_TNProblem * n)()
-        for e, (dy, N1, x, N2, Mw, out, bias, ld1, ld2, _) in zip(tab, problems):
-            e.dy, e.x, e.out, e.bias_out = ptr(dy), ptr(x), ptr(out), ptr(bias) if bias is not None else None
-            e.M, e.N1, e.N2, e.ld1, e.ld2 = Mw, N1, N2, ld1, ld2
-        ws = self.workspace(0)
-        need = lib.es_gemm_tn_big_grouped_workspace(ctypes.byref(tab), n, target)
-        if need > ws.numel():
-            raise RuntimeError(f"grouped weight-gradient workspace too small: {need} > {ws.numel()} floats")
-        raw = ctypes.create_string_buffer(lib.es_gemm_tn_big_grouped_table_bytes(n))
-        dims = (ctypes.c_int * 3)()
-        rc = lib.es_gemm_tn_big_grouped_prepare(ctypes.byref(tab), n, target, ptr(ws), ws.numel(), raw, dims)
-        if rc != 0:
-            raise _lib.EndosslLibraryError(f"es_gemm_tn_big_grouped_prepare: status {rc}")
+        n, workspace = len(problems), lambda need: self.workspace(0)
         pr = self.probe
         # probed at the launches sized like the timed ones: the CU-share-sized blocks (or every block of the
         # serial engine), not the first block's whole-chip launch at the end of an overlapped backward
@@ -982,7 +827,7 @@ class Engine:
             flop = sum(2.0 * q[4] * q[1] * q[3] for q in problems)
             # timed by the kernels' own start / end (hipExtLaunchKernelGGL events), as a kernel trace sees them
             e0, e1 = _lib.KernelEvent(), _lib.KernelEvent()
-            call("es_gemm_tn_big_grouped_timed", raw, n, dims, e0.handle, e1.handle, _lib.stream())
+            dims = block.tn_big_grouped(problems, target, workspace, timed=(e0, e1))
             pr["events"].append((e0, e1, flop))
             pr["layer_kernel"] = (f"es_gemm_tn_big_grouped: one block's {n} weight-gradient GEMMs "
                                   f"({'+'.join(str(q[1]) + 'x' + str(q[3]) for q in problems)}) over M={problems[0][4]} "
@@ -990,7 +835,7 @@ class Engine:
             pr["layer_bytes"] = sum(2.0 * q[4] * (q[1] + q[3]) + 4.0 * q[1] * q[3] + (4.0 * q[1] if q[6] is not None else 0)
                                     for q in problems)
         else:
-            call("es_gemm_tn_big_grouped", raw, n, dims, _lib.stream())
+            block.tn_big_grouped(problems, target, workspace)
 
     def _grouped_wgrad(self, M, grad_ready):
         if self.precision != "bf16" or grad_ready is not None:  # per-block hand-over needs per-layer launches
@@ -1002,17 +847,12 @@ class Engine:
         first).  The table's pointers are stable for a batch size (cached buffers), so the device copy
         (one per launch slot of the step) is re-made only when its bytes change."""
         problems = sorted(problems, key=lambda q: -q[4])
-        tab = (_TNProblem * len(problems))()
-        for e, (dy, N1, x, N2, Mw, out, bias, ld1, ld2) in zip(tab, problems):
-            e.dy, e.x, e.out, e.bias_out = ptr(dy), ptr(x), ptr(out), ptr(bias) if bias is not None else None
-            e.M, e.N1, e.N2, e.ld1, e.ld2 = Mw, N1, N2, ld1, ld2
+        tab = block.tn_table(problems)
         lib = _lib.load()
         tiles = lib.es_gemm_tn_grouped_prepare(ctypes.byref(tab), len(problems))
         if tiles <= 0:
             raise _lib.EndosslLibraryError(f"es_gemm_tn_grouped_prepare: status {tiles}")
         raw = bytes(tab)
-        if not hasattr(self, "_gtab"):
-            self._gtab = {}
         cache = self._gtab.get(slot)
         if cache is None or cache[0] != raw:
             if torch.cuda.is_current_stream_capturing():
@@ -1023,18 +863,10 @@ class Engine:
                                    "step of this shape first")
             dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device, non_blocking=False)
             self._gtab[slot] = cache = (raw, dev)
-        pr = self.probe
-        flop = sum(2.0 * q[4] * q[1] * q[3] for q in problems)
-        if pr is not None and pr["label"] == "fc1_wgrad":
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            call("es_gemm_tn_grouped", ptr(cache[1]), len(problems), tiles, _lib.stream())
-            e1.record()
-            pr["events"].append((e0, e1, flop))
+        pr = self._bracket("fc1_wgrad", sum(2.0 * q[4] * q[1] * q[3] for q in problems),
+                           lambda: call("es_gemm_tn_grouped", ptr(cache[1]), len(problems), tiles, _lib.stream()))
+        if pr is not None:
             pr["kernel"] = f"es_gemm_tn_grouped ({len(problems)} weight-gradient GEMMs, {tiles} tiles)"
-        else:
-            call("es_gemm_tn_grouped", ptr(cache[1]), len(problems), tiles, _lib.stream())
-
 
     def head_backward(self, flat, grad, dlogits, train=False):
         """IS_FREEZE (code/fixmatch.py:40-48: every parameter frozen but `model.fc`, timm's `head`):
