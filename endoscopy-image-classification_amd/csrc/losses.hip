@@ -8,6 +8,8 @@
 //  es_poly_ce_fwd_bwd         code/loss.py:103-114,308-364 (PolyLoss, softmax=True, epsilon=2):
 //      loss = mean_i( w[y_i] * CE_i + eps * (1 - p_i[y_i]) )   (plain mean, not weight-normalised)
 //      d/d l[i][c] = grad_scale * (w[y_i] + eps * p_i[y_i]) * (p_i[c] - [c == y_i])
+//  es_triplet_fwd_bwd         code/loss.py:170-190 (TripletLoss, alpha = 0.7) on z = [anchors; positives; negatives]
+//  es_softmax_predict         code/supervised.py:258-266 (inference: argmax, max probability, thresholded label)
 // The logits are tiny ([448,23] / [64,23]); one workgroup handles all rows, staging each row's
 // logits in registers, and emits int32 pseudo-labels, the uint8 mask, per-row losses and the two
 // means -- no host sync and no intermediate tensors.
@@ -168,6 +170,88 @@ __global__ __launch_bounds__(256) void ce_weight_sum_kernel(const int64_t* __res
   if (threadIdx.x == 0) out[0] = ws;
 }
 
+// TripletLoss (code/loss.py:170-190) on the L2-normalised embeddings, value and gradient; one workgroup,
+// one wave per triplet (wave w takes triplets w, w + nw, ...).  Lanes stride the L columns twice: the
+// squared distances, then -- the rows still in L1 -- the three gradient rows.  The four means are summed per
+// wave in triplet order and across waves in wave order: no atomics, the same bits on every launch.
+constexpr int TRIPLET_THREADS = 1024;
+
+__global__ __launch_bounds__(TRIPLET_THREADS) void triplet_kernel(const float* __restrict__ z, int ldz, int bs, int L,
+                                                                  float alpha, float grad_scale,
+                                                                  float* __restrict__ dz, int lddz,
+                                                                  float* __restrict__ out) {
+  __shared__ float red[16];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  float s_h = 0.f, s_p = 0.f, s_n = 0.f, s_act = 0.f;  // wave-uniform
+  for (int i = w; i < bs; i += nw) {
+    const float* za = z + (size_t)i * ldz;
+    const float* zp = z + (size_t)(bs + i) * ldz;
+    const float* zn = z + (size_t)(2 * bs + i) * ldz;
+    float sp = 0.f, sn = 0.f;
+    for (int k = lane; k < L; k += 64) {
+      const float a = za[k], ep = a - zp[k], en = a - zn[k];
+      sp = fmaf(ep, ep, sp);
+      sn = fmaf(en, en, sn);
+    }
+    const float dp = sqrtf(warp_sum(sp)), dn = sqrtf(warp_sum(sn));
+    const float h = dp - dn + alpha;
+    const bool act = h > 0.f;  // h == 0 is inactive
+    s_h += act ? h : 0.f;
+    s_p += dp;
+    s_n += dn;
+    s_act += act ? 1.f : 0.f;
+    // unit directions scaled by grad_scale; 0 at zero distance (torch.norm's backward) and for h <= 0
+    const float cp = act && dp > 0.f ? grad_scale / dp : 0.f;
+    const float cn = act && dn > 0.f ? grad_scale / dn : 0.f;
+    float* ga = dz + (size_t)i * lddz;
+    float* gp = dz + (size_t)(bs + i) * lddz;
+    float* gn = dz + (size_t)(2 * bs + i) * lddz;
+    for (int k = lane; k < L; k += 64) {
+      const float a = za[k], up = (a - zp[k]) * cp, un = (a - zn[k]) * cn;
+      ga[k] = up - un;
+      gp[k] = -up;
+      gn[k] = un;
+    }
+  }
+  const float inv = 1.0f / (float)bs;
+  s_h = block_sum(lane == 0 ? s_h : 0.f, red);
+  s_p = block_sum(lane == 0 ? s_p : 0.f, red);
+  s_n = block_sum(lane == 0 ? s_n : 0.f, red);
+  s_act = block_sum(lane == 0 ? s_act : 0.f, red);
+  if (threadIdx.x == 0) {
+    out[0] = s_h * inv;
+    out[1] = s_p * inv;
+    out[2] = s_n * inv;
+    out[3] = s_act * inv;
+  }
+}
+
+// softmax argmax / confidence / thresholded label per row (code/supervised.py:238-268, inference): a thread
+// per row, grid-stride over the rows.  conf = 1 / sum_c exp(l_c - max): the max's own probability.
+__global__ __launch_bounds__(256) void softmax_predict_kernel(const float* __restrict__ l, int ldl, int n, int C,
+                                                              float thres, int* __restrict__ pred,
+                                                              float* __restrict__ conf, int* __restrict__ label) {
+  const int stride = gridDim.x * blockDim.x;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float* lr = l + (size_t)i * ldl;
+    float mx = lr[0];
+    int idx = 0;
+    for (int c = 1; c < C; ++c) {
+      const float v = lr[c];
+      if (v > mx) {  // strict: the first index on ties
+        mx = v;
+        idx = c;
+      }
+    }
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += __expf(lr[c] - mx);
+    const float p = 1.0f / se;
+    if (pred) pred[i] = idx;
+    if (conf) conf[i] = p;
+    if (label) label[i] = p > thres ? idx : 0;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -222,6 +306,27 @@ int es_poly_ce_fwd_bwd(const float* logits, int ldl, const int64_t* targets, con
   if (!logits || !targets || !dlogits || !out) return ES_BAD_ARG;
   hipLaunchKernelGGL(poly_ce_kernel, 1, 256, 0, stream, logits, ldl, targets, weights, n, C, epsilon, grad_scale,
                      dlogits, lddl, out);
+  return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
+}
+
+// z [3 bs, L]: anchors, positives, negatives.  h_i = d_p,i - d_n,i + alpha; out = {mean max(h, 0), mean d_p,
+// mean d_n, fraction of h > 0}; dz = grad_scale * d(sum_i max(h_i, 0))/dz, every row written (zeros for h <= 0)
+int es_triplet_fwd_bwd(const float* z, int ldz, int bs, int L, float alpha, float grad_scale, float* dz, int lddz,
+                       float* out, hipStream_t stream) {
+  if (bs < 1 || bs > 0x7fffffff / 3 || L < 1 || L > 2048 || ldz < L || lddz < L) return ES_BAD_SHAPE;
+  if (!z || !dz || !out) return ES_BAD_ARG;
+  hipLaunchKernelGGL(triplet_kernel, 1, TRIPLET_THREADS, 0, stream, z, ldz, bs, L, alpha, grad_scale, dz, lddz, out);
+  return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
+}
+
+// pred = argmax (first index on ties), conf = max softmax probability, label = conf > thres ? pred : 0;
+// each output nullable, not all three
+int es_softmax_predict(const float* logits, int ldl, int n, int C, float thres, int* pred, float* conf, int* label,
+                       hipStream_t stream) {
+  if (n <= 0 || C <= 0 || C > MAXC || ldl < C) return ES_BAD_SHAPE;
+  if (!logits || (!pred && !conf && !label)) return ES_BAD_ARG;
+  const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
+  hipLaunchKernelGGL(softmax_predict_kernel, blocks, 256, 0, stream, logits, ldl, n, C, thres, pred, conf, label);
   return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
 }
 

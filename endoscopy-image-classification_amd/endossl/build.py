@@ -6,7 +6,9 @@ This factory returns the native ViT for the `vit_*` names instead (random timm-s
 checkpoint from MODEL.PRE_TRAIN_PATH loaded with weights_only=True, head dropped when its class
 count differs -- the reference re-heads abnormality checkpoints the same way, :180-194).
 For MODEL.TYPE_SEMI == 'CoMatch' it returns ModelwEmb over the native ViT (:175-178;
-comatch_model.NativeViTEmb, forward -> (logits, fts, z), LOW_DIM-d embedding).
+comatch_model.NativeViTEmb, forward -> (logits, fts, z), LOW_DIM-d embedding); the supervised
+triplet mode (MODEL.IS_TRIPLET without TRAIN.IS_SSL, :198-200) gets the same model with ModelwEmb's
+default 256-d embedding.
 For 'conformer' it returns the native Conformer-Ti of code/build.py:135-142 (patch 16,
 channel_ratio 1, embed 384, depth 12, 6 heads, qkv_bias; conformer.NativeConformer, forward ->
 (conv_logits, trans_logits)) -- SemiFormer's backbone.  CNN / Swin backbones are outside the
@@ -19,6 +21,7 @@ from .conformer import ConformerConfig, NativeConformer
 from .resnet import NativeResNet, ResNetConfig
 from .vit import VIT_CONFIGS, NativeViT, ViTConfig
 
+TRIPLET_LOW_DIM = 256  # ModelwEmb's default low_dim (code/models/custom_model.py:147)
 
 def build_model(config, is_pathology=True, seed=0):
     name = config.MODEL.NAME
@@ -45,11 +48,16 @@ def build_model(config, is_pathology=True, seed=0):
     if name not in VIT_CONFIGS:
         raise NotImplementedError(f"backbone {name!r}: native builds exist for {sorted(VIT_CONFIGS)}")
     comatch = getattr(config.MODEL, "TYPE_SEMI", "FixMatch") == "CoMatch" and getattr(config.TRAIN, "IS_SSL", True)
+    # code/build.py:198-200: ModelwEmb without a low_dim argument -- its default, MODEL.LOW_DIM is not read
+    triplet = (bool(getattr(config.MODEL, "IS_TRIPLET", False)) and not getattr(config.TRAIN, "IS_SSL", True)
+               and str(getattr(config.MODEL, "MARGIN", "None")) == "None")
     kw = dict(VIT_CONFIGS[name])
     if "IMG_SIZE" in config.DATA and int(config.DATA.IMG_SIZE) != kw["img_size"]:
         kw["img_size"] = int(config.DATA.IMG_SIZE)
     if comatch:
         model = NativeViTEmb(ViTConfig(num_classes=C, head="emb", low_dim=int(config.MODEL.LOW_DIM), **kw), seed=seed)
+    elif triplet:
+        model = NativeViTEmb(ViTConfig(num_classes=C, head="emb", low_dim=TRIPLET_LOW_DIM, **kw), seed=seed)
     else:
         model = NativeViT(ViTConfig(num_classes=C, **kw), seed=seed)
     path = getattr(config.MODEL, "PRE_TRAIN_PATH", "None")

@@ -11,8 +11,18 @@ train_one, evaluate_one, save_checkpoint, load_checkpoint, fit -- plus `step(bat
   bwd    autograd over the HIP ops
   opt    Adam + EMA of the parameters in one sweep, EMA of the BatchNorm buffers, LR update
 
-The margin (AngularPenaltySMLoss), triplet and mixup paths are out of the §8 scope
-and raise NotImplementedError.
+The triplet mode (MODEL.IS_TRIPLET, :84-108) runs on the embedding-head ViT (comatch_model.NativeViTEmb) as
+a direct launch sequence, no autograd:
+
+  fwd    (logits, fts, z) = model([anchors; poss; negs])     one trunk pass over 3 bs images
+  loss   ce = PolyCE(logits[:bs], y_a, w) (es_poly_ce_fwd_bwd); triplet = mean(max(d_p - d_n + 0.7, 0)) on z
+         (es_triplet_fwd_bwd); losses = ce + LAMBDA_C * triplet
+  bwd    heads backward -> dL/dfts -> trunk backward (model.backward_from)
+  opt    as above
+
+`test_one` (:198-236) and `inference` (:238-268, the pseudo-labelling pass; es_softmax_predict) take
+tuple-returning and plain-logit models.  The margin (AngularPenaltySMLoss) and mixup paths are out of the
+§8 scope and raise NotImplementedError.
 """
 import os
 from datetime import date, datetime
@@ -54,8 +64,15 @@ class SupLearning:
     def get_config(self, config):
         self.config = config
         print('Training mode: Supervised Learning')
-        if getattr(config.MODEL, "IS_TRIPLET", False) or str(getattr(config.MODEL, "MARGIN", "None")) != "None":
-            raise NotImplementedError("the triplet / angular-margin losses are outside the native step's scope")
+        if str(getattr(config.MODEL, "MARGIN", "None")) != "None":
+            raise NotImplementedError("the angular-margin losses are outside the native step's scope")
+        self.is_triplet = bool(getattr(config.MODEL, "IS_TRIPLET", False))
+        if self.is_triplet and getattr(getattr(self.model, "cfg", None), "head", None) != "emb":
+            raise ValueError("MODEL.IS_TRIPLET needs the embedding-head model (logits, fts, z): build it with "
+                             "build_model(config) with MODEL.IS_TRIPLET set and TRAIN.IS_SSL off")
+        self.triplet_alpha = 0.7  # TripletLoss(alpha=0.7) (code/supervised.py:60)
+        self.triplet_dist = {"d_ap": [], "d_an": []}
+        self._tws = {}
         dist.broadcast_(self.model.flat)
         self.model.mark_updated()
         self.ema_model = ModelEMA(model=self.model, decay=config.TRAIN.EMA_DECAY, device=self.device) \
@@ -126,8 +143,62 @@ class SupLearning:
         ent["graph"].replay()
         return tuple(t.clone() for t in ent["gout"])
 
-    def step(self, batch):
-        """batch = (images [n, 3, H, W], targets [n]) -> {"loss", "logits"} (device tensors)."""
+    def _triplet_workspace(self, bs, C, L):
+        """dl / dz of a batch shape.  dl's rows >= bs are zeroed here and never written: only the anchors'
+        logits enter the loss."""
+        key = (bs, C, L)
+        if key not in self._tws:
+            dev = self.model.flat.device
+            self._tws[key] = {"dl": torch.zeros(3 * bs, C, device=dev), "dz": torch.empty(3 * bs, L, device=dev)}
+        return self._tws[key]
+
+    def _step_triplet(self, batch, drop_keep=None):
+        """code/supervised.py:84-108 as a launch sequence (no autograd, no host sync)."""
+        (anchors, poss, negs), targets = batch
+        dev = self.model.flat.device
+        self._inflight.wait()
+        y = targets[0].to(dev, non_blocking=True).to(torch.int64).contiguous()  # the anchors' labels (:86)
+        imgs = [t.to(dev, non_blocking=True) for t in (anchors, poss, negs)]
+        bs = int(imgs[0].shape[0])
+        if any(int(t.shape[0]) != bs for t in imgs) or int(y.shape[0]) != bs:
+            raise ValueError("triplet batch: anchors, positives, negatives and the anchors' targets differ in length")
+        m, cfg = self.model, self.config
+        m.train()
+        C, L = m.cfg.num_classes, m.cfg.low_dim
+        s = _lib.stream()
+        W = self._triplet_workspace(bs, C, L)
+        dl, dz = W["dl"], W["dz"]
+        keep = None if drop_keep is None else drop_keep.to(dev, torch.uint8).contiguous()
+        logits, fts, z = m._run(imgs, train=True, keep=keep)
+        lam_c = float(cfg.TRAIN.LAMBDA_C)
+        stats = torch.empty(6, dtype=torch.float32, device=dev)  # ce, triplet, d_ap, d_an, active, total
+        call("es_poly_ce_fwd_bwd", ptr(logits), C, ptr(y), ptr(self.class_weights), bs, C, 2.0, 1.0 / bs, ptr(dl), C,
+             ptr(stats[0:1]), s)
+        call("es_triplet_fwd_bwd", ptr(z), L, bs, L, self.triplet_alpha, lam_c / bs, ptr(dz), L, ptr(stats[1:5]), s)
+        torch.add(stats[0], stats[1], alpha=lam_c, out=stats[5])
+        m.backward_from(dl, dz)
+        self._finish_step()
+        return {"loss": stats[5], "ce": stats[0], "triplet": stats[1], "d_ap": stats[2], "d_an": stats[3],
+                "active": stats[4], "logits": logits, "fts": fts, "z": z}
+
+    def _finish_step(self):
+        """Gradient all-reduce, optimizer + parameter EMA in one sweep, EMA of the BatchNorm buffers."""
+        gscale = dist.allreduce_sum_(self.model.flat_grad)
+        ema = self.ema_model
+        self.optimizer.step(ema_flat=ema.ema.flat if ema is not None else None,
+                            ema_decay=float(ema.decay) if ema is not None else 0.0, grad_scale=gscale)
+        if ema is not None:
+            ema.update_buffers(self.model)
+            ema.ema.mark_updated()
+        self._inflight.record()
+
+    def step(self, batch, drop_keep=None):
+        """batch = (images [n, 3, H, W], targets [n]) -> {"loss", "logits"} (device tensors).
+        Triplet mode: batch = ((anchors, poss, negs), (y_a, y_p, y_n)), each image tensor [bs, 3, H, W] ->
+        {"loss", "ce", "triplet", "d_ap", "d_an", "active", "logits", "fts", "z"}; drop_keep: optional uint8
+        [3 bs, D/4] Dropout keep-mask to replay (parity tests)."""
+        if getattr(self, "is_triplet", False):
+            return self._step_triplet(batch, drop_keep)
         images, targets = batch
         dev = self.model.flat.device
         self._inflight.wait()
@@ -139,39 +210,46 @@ class SupLearning:
             stats, logits = self._run_graph(images, targets)
         else:
             stats, logits = self._compute(images, targets)
-        gscale = dist.allreduce_sum_(self.model.flat_grad)
-        ema = self.ema_model
-        self.optimizer.step(ema_flat=ema.ema.flat if ema is not None else None,
-                            ema_decay=float(ema.decay) if ema is not None else 0.0, grad_scale=gscale)
-        if ema is not None:
-            ema.update_buffers(self.model)
-            ema.ema.mark_updated()
-        self._inflight.record()
+        self._finish_step()
         return {"loss": stats[0], "logits": logits.detach()}
 
     def train_one(self, epoch):
         self.model.train()
         summary_loss = AverageMeter()
         num_steps = len(self.train_dl)
-        pending = []
+        pending, dists = [], []
         for step, batch in enumerate(self.train_dl):
             out = self.step(batch)
             self.lr_scheduler.step_update(epoch * num_steps + step)
             pending.append(out["loss"].detach().clone())
+            if "d_ap" in out:  # triplet mode: the step's mean distances (code/supervised.py:99-100)
+                dists.append(torch.stack((out["d_ap"], out["d_an"])))
         for v in pending:  # one host sync per epoch
             summary_loss.update(v.item(), self.config.DATA.BATCH_SIZE)
+        if getattr(self, "is_triplet", False):
+            d = torch.stack(dists).cpu().tolist() if dists else []
+            self.triplet_dist = {"d_ap": [r[0] for r in d], "d_an": [r[1] for r in d]}
         return summary_loss
+
+    def _eval_model(self):
+        eval_model = self.ema_model.ema if self.config.TRAIN.USE_EMA else self.model
+        eval_model.eval()
+        return eval_model
+
+    @staticmethod
+    def _first(out):
+        """The logits of a model output: the first entry of ModelwEmb's (logits, fts, z)."""
+        return out[0] if isinstance(out, (tuple, list)) else out
 
     def evaluate_one(self, epoch=None, show_metric=False, show_report=False, show_cf_matrix=False):
         """code/supervised.py:148-196: unweighted CE mean, prediction = argmax softmax(logits)."""
-        eval_model = self.ema_model.ema if self.config.TRAIN.USE_EMA else self.model
-        eval_model.eval()
+        eval_model = self._eval_model()
         summary_loss = AverageMeter()
         outs, tgts = [], []
         dev = self.model.flat.device
         with torch.no_grad():
             for images, targets in self.valid_dl:
-                logits = eval_model(images.to(dev))
+                logits = self._first(eval_model(images.to(dev)))
                 targets = targets.to(dev).to(torch.int64).contiguous()
                 st = torch.zeros(1, device=dev)
                 scratch = torch.empty_like(logits)
@@ -189,6 +267,47 @@ class SupLearning:
             from sklearn.metrics import classification_report
             print(classification_report(tgt, pred))
         return summary_loss, metric
+
+    def _predict(self, logits, thres, want_label):
+        """es_softmax_predict on a batch of logits -> int32 device tensor (argmax, or the thresholded label)."""
+        logits = logits.float().contiguous()
+        n, C = logits.shape
+        res = torch.empty(n, dtype=torch.int32, device=logits.device)
+        call("es_softmax_predict", ptr(logits), C, n, C, float(thres), None if want_label else ptr(res), None,
+             ptr(res) if want_label else None, _lib.stream())
+        return res
+
+    def test_one(self, show_metric=False, show_report=False, show_cf_matrix=False):
+        """code/supervised.py:198-236: CPU bool tensor over valid_dl in loader order, True where the argmax
+        prediction differs from the target.  Predictions stay on the device until the one copy at the end."""
+        eval_model = self._eval_model()
+        dev = self.model.flat.device
+        wrong = []
+        with torch.no_grad():
+            for images, targets in self.valid_dl:
+                logits = self._first(eval_model(images.to(dev, non_blocking=True)))
+                pred = self._predict(logits, 0.0, want_label=False)
+                wrong.append(pred != targets.to(dev, non_blocking=True).view(-1).to(torch.int32))
+        if not wrong:
+            return torch.zeros(0, dtype=torch.bool)
+        return torch.cat(wrong).cpu()
+
+    def inference(self, dl_test):
+        """code/supervised.py:238-268: {index: label} over dl_test's (images, index) batches, label =
+        argmax(p) where max(p) > TRAIN.THRES (strict) and 0 below it -- class 0, the reference's
+        `argmax * cond`.  One device-to-host copy at the end."""
+        eval_model = self._eval_model()
+        dev = self.model.flat.device
+        thres = float(self.config.TRAIN.THRES)
+        labels, index = [], []
+        with torch.no_grad():
+            for images, idx in dl_test:
+                logits = self._first(eval_model(images.to(dev, non_blocking=True)))
+                labels.append(self._predict(logits, thres, want_label=True))
+                index += idx.tolist() if torch.is_tensor(idx) else np.array(idx).tolist()
+        if not labels:
+            return {}
+        return dict(zip(index, torch.cat(labels).cpu().tolist()))
 
     def save_checkpoint(self, foldname):
         """Same dict keys and filename scheme as code/supervised.py:271-293."""

@@ -307,6 +307,19 @@ int es_fm_consistency_fwd_bwd(const float* logits_w, int ldw, const float* logit
 int es_poly_ce_fwd_bwd(const float* logits, int ldl, const int64_t* targets, const float* weights, int n, int C,
                        float epsilon, float grad_scale, float* dlogits, int lddl, float* out, hipStream_t stream);
 
+/* ---- supervised triplet mode (code/supervised.py:84-108,238-268) ------------------------------- */
+/* code/loss.py:170-190 TripletLoss on z [3 bs, L] fp32, rows [0,bs) anchors, [bs,2bs) positives, [2bs,3bs)
+ * negatives: h_i = |z_a - z_p| - |z_a - z_n| + alpha; out[0] = mean max(h_i, 0), out[1] = mean d_p,
+ * out[2] = mean d_n, out[3] = fraction of h_i > 0.  dz = grad_scale * d(sum_i max(h_i, 0))/dz -- pass
+ * lambda_c / bs; every row is written (zeros where h_i <= 0; a unit direction is 0 at distance 0).
+ * 1 <= L <= 2048; no atomics: repeated launches give the same bits */
+int es_triplet_fwd_bwd(const float* z, int ldz, int bs, int L, float alpha, float grad_scale, float* dz, int lddz,
+                       float* out, hipStream_t stream);
+/* per row of logits [n, C <= 64]: pred = argmax (first index on ties), conf = max softmax probability,
+ * label = conf > thres ? pred : 0 (code/supervised.py:258-266); each output nullable, not all three */
+int es_softmax_predict(const float* logits, int ldl, int n, int C, float thres, int* pred, float* conf, int* label,
+                       hipStream_t stream);
+
 /* ---- Conformer CNN branch (SemiFormer backbone, code/models/conformer.py:75-445) ---------------
  * fp32 NHWC maps with element strides; Conv2d groups = 1, weights in the reference layout
  * [Cout][Cin][kh][kw].  Replaces the reference's aten conv2d / batch_norm / max_pool2d /
