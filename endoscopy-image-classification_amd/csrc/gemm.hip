@@ -16,6 +16,7 @@
 // step k+1 is issued before the MFMAs of step k.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include <hip/hip_ext.h>
 
@@ -1591,6 +1592,51 @@ __device__ __forceinline__ float mul_rounded(float a, float b) {
   return a * b;
 }
 
+// One row of the D = 384 LayerNorm held by a wave in ln_fwd_kernel's lane map (v[j]: columns (j * 64 + lane) * 2,
+// + 1): the row's mean / rstd and the lane's three bf16 output pairs, shared by the fused GEMM + LayerNorm kernels
+// below.  The statistics carry the rounding of ln_fwd_kernel / ln_fwd_loop_kernel as hipcc (ROCm 7.2) compiles
+// them, which differs between the two rows a wave holds there (even: the first row of the pair, i.e. an even
+// token row): their ISA sums the three column pairs' squares as fma(a0, a0, b0 b0) + (a1 a1 + b1 b1) +
+// fma(a2, a2, b2 b2) for the even row and with no fma for the odd row, left to right, fuses the variance scale
+// with eps and forms the output as fma(g, (x - mean) rstd, b).  Written out because where hipcc contracts
+// a * b + c depends on the surrounding code (the same source expression gave rstd 1 ulp apart on ~2 % of rows);
+// the bit-identity tests (test_gemm_resid_ln_matches_two_launches_bit_for_bit, tests/test_gpu_fc2_ln.py) pin it to
+// the LayerNorm kernels' build.
+struct LnRow384 {
+  float mean, rstd;
+  unsigned h[3];  // bf16 pairs
+};
+__device__ __forceinline__ LnRow384 ln_row384(const float2 (&v)[3], bool even, float eps, const float* gam_lds,
+                                              const float* bet_lds, int lane) {
+  constexpr int D = 384;
+  LnRow384 o;
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) s += v[j].x + v[j].y;
+  o.mean = warp_sum(s) * (1.0f / D);
+  float a[3], b[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    a[j] = v[j].x - o.mean;
+    b[j] = v[j].y - o.mean;
+  }
+  const float t0 = even ? sq2_fused(a[0], b[0]) : sq2_rounded(a[0], b[0]);
+  const float t1 = sq2_rounded(a[1], b[1]);
+  const float t2 = even ? sq2_fused(a[2], b[2]) : sq2_rounded(a[2], b[2]);
+  const float ss = (t0 + t1) + t2;
+  o.rstd = 1.0f / sqrtf(__builtin_fmaf(warp_sum(ss), 1.0f / D, eps));
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int c = (j * 64 + lane) * 2;
+    const float2 gm = *(const float2*)(gam_lds + c), bt = *(const float2*)(bet_lds + c);
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    const bf16x2 h = {(bf16)__builtin_fmaf(mul_rounded(a[j], o.rstd), gm.x, bt.x),
+                      (bf16)__builtin_fmaf(mul_rounded(b[j], o.rstd), gm.y, bt.y)};
+    o.h[j] = __builtin_bit_cast(unsigned, h);
+  }
+  return o;
+}
+
 struct RLArgs {
   const float* gamma; const float* beta;
   bf16* h; float* mean; float* rstd;
@@ -1734,48 +1780,21 @@ __global__ __launch_bounds__(512, 1) void gemm_resid_ln_kernel(NTArgs p, RLArgs 
           const int cc = (j * 64 + lane) >> 1;
           v[j] = *(const float2*)(X + row * ROWX + ((cc ^ (row & 15)) << 4) + (lane & 1) * 8);
         }
-        // the statistics with the rounding of ln_fwd_kernel / ln_fwd_loop_kernel as hipcc (ROCm 7.2) compiles
-        // them, which differs between the two rows a wave holds: their ISA sums the three column pairs' squares
-        // as fma(a0, a0, b0 b0) + (a1 a1 + b1 b1) + fma(a2, a2, b2 b2) for the even row and with no fma for the
-        // odd row, left to right, fuses the variance scale with eps and forms the output as fma(g, (x - mean)
-        // rstd, b).  Written out here because where hipcc contracts a * b + c depends on the surrounding code
-        // (the same source expression gave rstd 1 ulp apart on ~2 % of rows); the bit-identity test
-        // (test_gemm_resid_ln_matches_two_launches_bit_for_bit) pins it to the LayerNorm kernels' build.
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) s += v[j].x + v[j].y;
-        const float mean = warp_sum(s) * (1.0f / D);
-        float a[3], b[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          a[j] = v[j].x - mean;
-          b[j] = v[j].y - mean;
-        }
-        const bool even = (q & 1) == 0;  // the row's place in ln_fwd_kernel's row pair (m0 and w * 4 are even)
-        const float t0 = even ? sq2_fused(a[0], b[0]) : sq2_rounded(a[0], b[0]);
-        const float t1 = sq2_rounded(a[1], b[1]);
-        const float t2 = even ? sq2_fused(a[2], b[2]) : sq2_rounded(a[2], b[2]);
-        const float ss = (t0 + t1) + t2;
-        const float rstd = 1.0f / sqrtf(__builtin_fmaf(warp_sum(ss), 1.0f / D, l.eps));
+        const LnRow384 o = ln_row384(v, (q & 1) == 0, l.eps, gam_lds, bet_lds, lane);  // m0 and w * 4 are even
         const int m = m0 + row;
         const bool ok = m < p.M;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
           const int c = (j * 64 + lane) * 2;
-          const float2 gm = *(const float2*)(gam_lds + c), bt = *(const float2*)(bet_lds + c);
-          typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-          bf16x2 o = {(bf16)__builtin_fmaf(mul_rounded(a[j], rstd), gm.x, bt.x),
-                      (bf16)__builtin_fmaf(mul_rounded(b[j], rstd), gm.y, bt.y)};
           __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v[j]), rx,
                                                 ok ? (unsigned)(m * p.ldc + c) * 4u : ES_OOB, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), rh,
-                                                ok ? (unsigned)(m * l.ldh + c) * 2u : ES_OOB, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(o.h[j], rh, ok ? (unsigned)(m * l.ldh + c) * 2u : ES_OOB, 0, 0);
         }
         const bool one = ok && lane == 0;
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, mean), rm, one ? (unsigned)m * 4u : ES_OOB,
-                                              0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, rstd), rs, one ? (unsigned)m * 4u : ES_OOB,
-                                              0, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o.mean), rm,
+                                              one ? (unsigned)m * 4u : ES_OOB, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o.rstd), rs,
+                                              one ? (unsigned)m * 4u : ES_OOB, 0, 0);
       }
       seq += 4 * 8;
       if (claimer) {  // publish the tile of step it + 2
@@ -1786,6 +1805,222 @@ __global__ __launch_bounds__(512, 1) void gemm_resid_ln_kernel(NTArgs p, RLArgs 
       }
       st ^= 1;
     }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (tid == 0) {
+    const int d = __hip_atomic_fetch_add(ctr + SLOT_INTS - 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (d == (int)gridDim.x - 1) {
+      __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(ctr + SLOT_INTS - 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The MLP's fc2 with its residual add AND the next block's LayerNorm 1 (es_gemm_nt_ln): x = act W^T + b + xmid
+// (fp32), h = LN(x) (bf16), mean / rstd -- for N = 384 and any K % 64 == 0 (ViT-S fc2: K = 1536).  Replaces
+// es_gemm_nt(EPI_F32_RESID) + es_layernorm_fwd (code/models/conformer.py:70-71 then :65 of the next block) in one
+// pass: the x this block writes is not re-read for the next block's statistics.
+//   Main loop: the big-tile family's at 128 x 384 (gemm_nt_big_kernel's WM = 2, MF = 4, NF = 6: 8 waves of
+//     64 x 96), whole rows per workgroup, the same MFMA and ascending-K order as every NT kernel, so x carries
+//     es_gemm_nt(EPI_F32_RESID)'s bits.  Ring: BKT 64 x 2 stages (128 KiB) or BKT 32 x 3 stages (96 KiB).
+//   Tiles: one persistent workgroup per CU claims 128-row tiles from a per-stream counter (g_nl_ctr, reset by the
+//     last workgroup out: capturable); the next claim is issued after the K loop and read after the epilogue.
+//   Epilogue: the ring is free once every wave has left the K loop; the tile goes through it in two 64-row slabs
+//     (slab s: each wave's row blocks 2 s, 2 s + 1; 96 KiB, gemm_resid_ln_kernel's chunk ^ (row & 15) layout):
+//     acc + bias written in the MFMA layout, barrier, then one wave per row (8 rows per wave and slab) adds the
+//     residual -- loaded straight from memory in the LayerNorm's lane map, whole 1,536-B rows, four rows ahead --
+//     and runs ln_row384; x, h, mean, rstd stored as whole rows.  Rows >= M are never stored; their A / residual
+//     rows re-read row M - 1.
+namespace nlg {
+constexpr int TBM = 128, D = 384, WN = 4, MF = 4, NF = 6;
+constexpr int SLABR = 64, ROWX = D * 4, SLAB = SLABR * ROWX;  // 96 KiB
+constexpr int RPS = SLABR / 8;                                // LayerNorm rows per wave and slab
+constexpr int SLOTS = 64, SLOT_INTS = 4;                      // per stream: [0] head, [3] done
+template <int NST, int BKT>
+constexpr int body() { return NST * (TBM + D) * BKT * 2 > SLAB ? NST * (TBM + D) * BKT * 2 : SLAB; }
+template <int NST, int BKT>
+constexpr int lds() { return body<NST, BKT>() + 16 + D * 4 * 3; }  // ring / slab, the claim, bias, gamma, beta
+}  // namespace nlg
+__device__ int g_nl_ctr[nlg::SLOTS * nlg::SLOT_INTS];
+
+template <int NST, int BKT>
+__global__ __launch_bounds__(512, 1) void gemm_nt_ln_kernel(NTArgs p, RLArgs l, int slot) {
+  using namespace nlg;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int ROWB = BKT * 2, RPI = 1024 / ROWB, CPR = ROWB / 16, RPW = 8 * RPI;
+  constexpr int IA = TBM / RPW, IB = D / RPW, PER = IA + IB;
+  static_assert(TBM % RPW == 0 && D % RPW == 0, "tile");
+  constexpr int TA = TBM * ROWB, STAGE = (TBM + D) * ROWB;
+  int* const qslot = (int*)(smem + body<NST, BKT>());
+  float* const bias_lds = (float*)(smem + body<NST, BKT>() + 16);
+  float* const gam_lds = bias_lds + D;
+  float* const bet_lds = gam_lds + D;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = w / WN, wn = w % WN;
+  const int g = lane >> 4, r = lane & 15;
+  int* const ctr = g_nl_ctr + slot * SLOT_INTS;
+  const int nt = (p.M + TBM - 1) / TBM;
+  if (tid == 0) qslot[0] = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid < D / 4) {
+    *(f32x4*)(bias_lds + 4 * tid) = p.bias ? *(const f32x4*)(p.bias + 4 * tid) : f32x4{0.f, 0.f, 0.f, 0.f};
+    *(f32x4*)(gam_lds + 4 * tid) = *(const f32x4*)(l.gamma + 4 * tid);
+    *(f32x4*)(bet_lds + 4 * tid) = *(const f32x4*)(l.beta + 4 * tid);
+  }
+  __syncthreads();
+  int cur = __builtin_amdgcn_readfirstlane(qslot[0]);
+
+  const bf16* gb[IB];
+  int arow[IA], acol[IA];
+#pragma unroll
+  for (int j = 0; j < IB; ++j) {
+    const int row = (j * 8 + w) * RPI + lane / CPR;
+    gb[j] = p.B + (size_t)row * p.ldb + swzk<BKT>(row, lane % CPR) * 8;
+  }
+#pragma unroll
+  for (int j = 0; j < IA; ++j) {
+    arow[j] = (j * 8 + w) * RPI + lane / CPR;
+    acol[j] = swzk<BKT>(arow[j], lane % CPR) * 8;
+  }
+  const unsigned rows = (unsigned)p.M;
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(p.C, rows * p.ldc * 4u);
+  const __amdgpu_buffer_rsrc_t rh = buf_rsrc(l.h, rows * l.ldh * 2u);
+  const __amdgpu_buffer_rsrc_t rm = buf_rsrc(l.mean, rows * 4u);
+  const __amdgpu_buffer_rsrc_t rs = buf_rsrc(l.rstd, rows * 4u);
+  const float* const resid = (const float*)p.aux;
+  const int nk = p.K / BKT;
+
+  while (cur < nt) {
+    const int m0 = cur * TBM, last = p.M - 1;
+    // the tile row of this wave's LayerNorm row q of slab s: slab row w * 8 + q = 32 wm' + 16 mi' + r'
+    auto tile_row = [&](int s, int q) {
+      const int lr = w * RPS + q;
+      return (lr >> 5) * 64 + s * 32 + (lr & 31);
+    };
+    // the residual rows of this wave's LayerNorm rows, in four groups of RPS / 2 (group 2 s + h: rows 4 h .. + 3 of
+    // slab s), each loaded one group ahead of its use: 24 registers in flight beside the accumulators
+    float2 rv[4][RPS / 2][3];
+    auto load_resid = [&](auto gc) {
+      constexpr int gi = decltype(gc)::value;
+#pragma unroll
+      for (int q = 0; q < RPS / 2; ++q) {
+        const float* xr = resid + (size_t)min(m0 + tile_row(gi >> 1, (gi & 1) * (RPS / 2) + q), last) * p.ldaux;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) rv[gi][q][j] = *(const float2*)(xr + (j * 64 + lane) * 2);
+      }
+    };
+    load_resid(std::integral_constant<int, 0>{});  // behind the K loop
+
+    const bf16* ga[IA];
+#pragma unroll
+    for (int j = 0; j < IA; ++j) ga[j] = p.A + (size_t)min(m0 + arow[j], last) * p.lda + acol[j];
+#define NL_ISSUE(BUF, K0)                                                                                \
+  {                                                                                                      \
+    char* S_ = smem + (BUF) * STAGE;                                                                     \
+    _Pragma("unroll") for (int j = 0; j < IA; ++j) glds16(ga[j] + (K0), S_ + (j * 8 + w) * 1024);        \
+    _Pragma("unroll") for (int j = 0; j < IB; ++j) glds16(gb[j] + (K0), S_ + TA + (j * 8 + w) * 1024);   \
+  }
+    f32x4 acc[MF][NF];
+#pragma unroll
+    for (int i = 0; i < MF; ++i)
+#pragma unroll
+      for (int j = 0; j < NF; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int st = 0; st < NST - 1; ++st)
+      if (st < nk) NL_ISSUE(st, st * BKT)
+    int buf = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+      wait_vmcnt(min(NST - 2, nk - 1 - kt) * PER);
+      __builtin_amdgcn_s_barrier();
+      if (kt + NST - 1 < nk) {
+        int nb = buf + NST - 1;
+        nb = nb >= NST ? nb - NST : nb;
+        NL_ISSUE(nb, (kt + NST - 1) * BKT)
+      }
+      const char* As = smem + buf * STAGE;
+      const char* Bs = As + TA;
+#pragma unroll
+      for (int kk = 0; kk < BKT / 32; ++kk) {
+        bf16x8 af[MF], bfr[NF];
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+          const int rb = wn * NF * 16 + j * 16 + r;
+          bfr[j] = *(const bf16x8*)(Bs + rb * ROWB + swzk<BKT>(rb, kk * 4 + g) * 16);
+        }
+#pragma unroll
+        for (int i = 0; i < MF; ++i) {
+          const int ra = wm * MF * 16 + i * 16 + r;
+          af[i] = *(const bf16x8*)(As + ra * ROWB + swzk<BKT>(ra, kk * 4 + g) * 16);
+        }
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int i = 0; i < MF; ++i)
+#pragma unroll
+          for (int j = 0; j < NF; ++j) acc[i][j] = mfma16(bfr[j], af[i], acc[i][j]);
+        __builtin_amdgcn_s_setprio(0);
+      }
+      buf = buf + 1 == NST ? 0 : buf + 1;
+    }
+#undef NL_ISSUE
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // every wave has left the K loop: the ring is free
+    int claimed = 0;
+    if (tid == 0) claimed = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    load_resid(std::integral_constant<int, 1>{});
+
+    auto slab = [&](auto sc) {
+      constexpr int s = decltype(sc)::value;
+      // acc + bias in the MFMA layout: slab row 32 wm + 16 i + r, columns wn * 96 + 16 j + 4 g .. + 3
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+          const int lr = wm * 32 + i * 16 + r, c = wn * NF * 4 + 4 * j + g;
+          *(f32x4*)(smem + lr * ROWX + ((c ^ r) << 4)) =
+              acc[2 * s + i][j] + *(const f32x4*)(bias_lds + wn * NF * 16 + 16 * j + 4 * g);
+        }
+      if constexpr (s == 0) load_resid(std::integral_constant<int, 2>{});
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();  // the slab complete
+#pragma unroll
+      for (int q = 0; q < RPS; ++q) {
+        const int lr = w * RPS + q;
+        float2 v[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const int cc = (j * 64 + lane) >> 1;
+          const float2 t = *(const float2*)(smem + lr * ROWX + ((cc ^ (lr & 15)) << 4) + (lane & 1) * 8);
+          const float2 rr = rv[2 * s + q / (RPS / 2)][q % (RPS / 2)][j];
+          v[j] = make_float2(t.x + rr.x, t.y + rr.y);  // (acc + bias) + residual
+        }
+        if constexpr (s == 0)
+          if (q == RPS / 2 - 1) load_resid(std::integral_constant<int, 3>{});
+        const LnRow384 o = ln_row384(v, (q & 1) == 0, l.eps, gam_lds, bet_lds, lane);  // m0 and w * 8 are even
+        const int m = m0 + tile_row(s, q);
+        const bool ok = m < p.M;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const int c = (j * 64 + lane) * 2;
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v[j]), rx,
+                                                ok ? (unsigned)(m * p.ldc + c) * 4u : ES_OOB, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(o.h[j], rh, ok ? (unsigned)(m * l.ldh + c) * 2u : ES_OOB, 0, 0);
+        }
+        const bool one = ok && lane == 0;
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o.mean), rm,
+                                              one ? (unsigned)m * 4u : ES_OOB, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o.rstd), rs,
+                                              one ? (unsigned)m * 4u : ES_OOB, 0, 0);
+      }
+    };
+    slab(std::integral_constant<int, 0>{});
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // slab 0 read by every wave
+    slab(std::integral_constant<int, 1>{});
+    if (tid == 0) qslot[0] = claimed;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // slab 1 read, the next tile published
+    cur = __builtin_amdgcn_readfirstlane(qslot[0]);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (tid == 0) {
@@ -1934,6 +2169,27 @@ int launch_resid_ln(hipStream_t stream, const NTArgs& a, const RLArgs& l) {
   return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
 }
 
+int launch_nt_ln(int ring, hipStream_t stream, const NTArgs& a, const RLArgs& l) {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  }
+  const int nt = (a.M + nlg::TBM - 1) / nlg::TBM;
+  const int grid = std::max(1, std::min(cus, nt));
+  const int slot = ws_slot(stream);
+  constexpr size_t lds3 = nlg::lds<3, 32>(), lds2 = nlg::lds<2, 64>();
+  if (ring == 1) {  // BKT 32 x 3 stages
+    allow_lds(gemm_nt_ln_kernel<3, 32>, lds3);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_nt_ln_kernel<3, 32>), dim3(grid), dim3(512), lds3, stream, a, l, slot);
+  } else {  // BKT 64 x 2 stages
+    allow_lds(gemm_nt_ln_kernel<2, 64>, lds2);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_nt_ln_kernel<2, 64>), dim3(grid), dim3(512), lds2, stream, a, l, slot);
+  }
+  return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
+}
+
 }  // namespace es_gemm
 using namespace es_gemm;
 
@@ -2062,6 +2318,34 @@ int es_gemm_nt_resid_ln(const void* A, int lda, const void* B, int ldb, const fl
   NTArgs a{(const bf16*)A, (const bf16*)B, bias, C, nullptr, aux, M, N, K, lda, ldb, ldc, ldaux, 0};
   RLArgs l{gamma, beta, (bf16*)h, mean, rstd, ldh, eps};
   return launch_resid_ln(stream, a, l);
+}
+
+// x = A B^T + bias + aux (fp32 residual), h = LayerNorm(x; gamma, beta) (bf16) with its per-row mean / rstd, for
+// N = 384 and K % 64 == 0 (gemm_nt_ln_kernel; the ViT MLP's fc2 with the next block's LayerNorm 1):
+// es_gemm_nt(EPI_F32_RESID) followed by es_layernorm_fwd in one launch, the same bits.
+static int g_nt_ln_ring = 0;
+int es_gemm_nt_ln(const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc,
+                  const float* aux, int ldaux, const float* gamma, const float* beta, void* h, int ldh, float* mean,
+                  float* rstd, int M, int N, int K, float eps, hipStream_t stream) {
+  if (M <= 0 || N != nlg::D || K <= 0 || (K % 64) || (lda % 8) || (ldb % 8) || (ldc % 2) || (ldaux % 2) || (ldh % 2) ||
+      lda < K || ldb < K || ldc < N || ldaux < N || ldh < N ||
+      (size_t)M * (size_t)std::max(std::max(ldc, ldaux), ldh) * 4 >= (1u << 31))
+    return ES_BAD_SHAPE;
+  if (!A || !B || !C || !aux || !gamma || !beta || !h || !mean || !rstd) return ES_BAD_ARG;
+  // 16-B pieces by LDS-DMA (A, B), 16-B parameter loads, 8-B residual loads and x stores, 4-B h stores
+  if ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)gamma | (uintptr_t)beta) & 15) || (bias && ((uintptr_t)bias & 15)) ||
+      (((uintptr_t)C | (uintptr_t)aux) & 7) || (((uintptr_t)h | (uintptr_t)mean | (uintptr_t)rstd) & 3))
+    return ES_BAD_ARG;
+  NTArgs a{(const bf16*)A, (const bf16*)B, bias, C, nullptr, aux, M, N, K, lda, ldb, ldc, ldaux, 0};
+  RLArgs l{gamma, beta, (bf16*)h, mean, rstd, ldh, eps};
+  return launch_nt_ln(g_nt_ln_ring, stream, a, l);
+}
+// measurement only (scripts/fc2_ln_bench.py; not part of the es_ ABI): es_gemm_nt_ln's ring, 0 = BKT 64 x 2 stages
+// (the default), 1 = BKT 32 x 3 stages.  Returns the previous value.
+int endossl_nt_ln_ring(int v) {
+  const int old = g_nt_ln_ring;
+  g_nt_ln_ring = v == 1 ? 1 : 0;
+  return old;
 }
 
 // Tuning knob: which NT kernel family es_gemm_nt launches (-1 = per-shape default, 0 = 128x128

@@ -33,6 +33,13 @@ def gemm_nt_resid_ln(call, a, w, bias, xmid, xin, gamma, beta, h, mean, rstd, M,
          stream() if s is None else s)
 
 
+def gemm_nt_ln(call, a, w, bias, xout, xmid, gamma, beta, h, mean, rstd, M, N, K, eps, s=None):
+    """xout = xmid + a w^T + bias and h, mean, rstd = LayerNorm(xout) in one launch (N = 384, K % 64 == 0)."""
+    call("es_gemm_nt_ln", ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(xout), xout.stride(0), ptr(xmid),
+         xmid.stride(0), ptr(gamma), ptr(beta), ptr(h), h.stride(0), ptr(mean), ptr(rstd), M, N, K, eps,
+         stream() if s is None else s)
+
+
 def layernorm_fwd(call, x, gamma, beta, y, mean, rstd, M, D, eps, s=None):
     call("es_layernorm_fwd", ptr(x), x.stride(0), ptr(gamma), ptr(beta), ptr(y), y.stride(0), ptr(mean), ptr(rstd), M,
          D, eps, stream() if s is None else s)
@@ -98,11 +105,14 @@ class Chain:
         self.epi_dh = EPI_BF16 if dh_bf16 else EPI_F32  # d(LN output) from the fc1 / qkv data gradients
         self.bracket = bracket  # the owner's launch of a labelled site (Engine._bracket: timed when probed)
 
-    def attn_fwd(self, b, R, cls=None, split_q=False):
+    def attn_fwd(self, b, R, cls=None, split_q=False, ln_done=False):
         """LN1 -> qkv GEMM -> attention.  cls (a pruned last block's compact row set): the CLS queries' attention
-        only, into cls.o / cls.lse; split_q: Q for the CLS rows only (gathered into cls.h1), onto their rows of qkv."""
+        only, into cls.o / cls.lse; split_q: Q for the CLS rows only (gathered into cls.h1), onto their rows of qkv;
+        ln_done: R.h1 / R.mean1 / R.rstd1 are there already (the previous block's mlp_fwd(next_ln=) wrote them)."""
         call, p, s, M, D = self.call, self.p, stream(), R.rows, R.h1.shape[1]
-        layernorm_fwd(call, R.x, p(b + "norm1.weight"), p(b + "norm1.bias"), R.h1, R.mean1, R.rstd1, M, D, self.eps, s)
+        if not ln_done:
+            layernorm_fwd(call, R.x, p(b + "norm1.weight"), p(b + "norm1.bias"), R.h1, R.mean1, R.rstd1, M, D,
+                          self.eps, s)
         w, bias = self.wb[b + "attn.qkv.weight"], p(b + "attn.qkv.bias")
         if cls is not None and split_q:
             gemm_nt(call, EPI_BF16, R.h1, w[D:], bias[D:], R.qkv[:, D:], M, 2 * D, D, s=s)
@@ -113,9 +123,11 @@ class Chain:
         Ro = R if cls is None else cls
         attn_fwd(call, R.qkv, Ro.o, Ro.lse, R.n, R.T, self.heads, s, cls is not None)
 
-    def mlp_fwd(self, b, R, train, fused=False, label=None):
+    def mlp_fwd(self, b, R, train, fused=False, label=None, next_ln=None):
         """proj + residual -> LN2 -> fc1 -> fc2 (fused: the first two as one es_gemm_nt_resid_ln launch).  train:
-        fc1 keeps R.pre for the backward beside R.act; label: the fc1 launch goes through the owner's bracket."""
+        fc1 keeps R.pre for the backward beside R.act; label: the fc1 launch goes through the owner's bracket.
+        next_ln = (gamma, beta, h1, mean1, rstd1) of the next block: fc2, its residual add and that block's
+        LayerNorm 1 as one es_gemm_nt_ln launch (the next attn_fwd then takes ln_done=True)."""
         call, p, wb, s, M = self.call, self.p, self.wb, stream(), R.rows
         D, Hd = R.h2.shape[1], R.act.shape[1]
         if fused:
@@ -130,6 +142,11 @@ class Chain:
         fc1 = lambda: gemm_nt(call, epi, R.h2, wb[b + "mlp.fc1.weight"], p(b + "mlp.fc1.bias"), c, M, Hd, D,  # noqa: E731
                               c2=c2, s=s)
         self.bracket(label, 2.0 * M * Hd * D, fc1)
+        if next_ln is not None:
+            gamma, beta, h1, mean1, rstd1 = next_ln
+            gemm_nt_ln(call, R.act, wb[b + "mlp.fc2.weight"], p(b + "mlp.fc2.bias"), R.out, R.xmid, gamma, beta, h1,
+                       mean1, rstd1, M, D, Hd, self.eps, s)
+            return
         gemm_nt(call, EPI_F32_RESID, R.act, wb[b + "mlp.fc2.weight"], p(b + "mlp.fc2.bias"), R.out, M, D, Hd,
                 aux=R.xmid, s=s)
 

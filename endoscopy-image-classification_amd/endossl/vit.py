@@ -292,6 +292,18 @@ class Engine:
     # turns it off.
     RESID_LN = os.environ.get("ENDOSSL_RESID_LN", "1") == "1"
     RESID_LN_MIN_M = 40000
+    # the MLP's fc2, its residual add and the NEXT block's LayerNorm 1 as one launch (es_gemm_nt_ln: the block
+    # output is not re-read for the next block's statistics; the same bits as the two launches, tested) at D = 384
+    # for token axes of at least FC2_LN_MIN_M rows, blocks 0 .. depth - 2; FC2_LN_TRAIN / FC2_LN_WEAK: the train
+    # (saved activations) and the weak (inference) pass each by its own measurement (scripts/fc2_ln_bench.py,
+    # scripts/gpu_ab_fc2ln.sh; profiles/fc2_ln_ab.txt).  Isolated 215 -> 182 us at F1's weak rows, 236 -> 233 at the
+    # train rows, mixed at a rank's share at N = 2 and slower at N = 8 (35 -> 48); F1 29.73 / 29.66 / 29.62 ->
+    # 29.04 / 29.02 / 28.98 ms with both passes, 29.54 / 29.47 / 29.44 with the weak pass alone (same box,
+    # interleaved).  ENDOSSL_FC2_LN=0 turns it off.
+    FC2_LN = os.environ.get("ENDOSSL_FC2_LN", "1") == "1"
+    FC2_LN_MIN_M = 50000
+    FC2_LN_TRAIN = True
+    FC2_LN_WEAK = True
 
     # fp32 parity mode (csrc/parity.hip): the same launch sequence over fp32 operand storage; the
     # entry points with an fp32 form, by their bf16 names
@@ -467,6 +479,9 @@ class Engine:
         prune = self._prune()
         ch = self._chain(flat)
         fused = self.RESID_LN and D == 384 and self.precision == "bf16" and M >= self.RESID_LN_MIN_M
+        fc2_ln = (self.FC2_LN and (self.FC2_LN_TRAIN if train else self.FC2_LN_WEAK) and D == 384
+                  and self.precision == "bf16" and M >= self.FC2_LN_MIN_M)
+        ln_done = False  # this block's LayerNorm 1 came out of the previous block's fc2 launch
         for i in range(cfg.depth):
             b = f"blocks.{i}."
             li = i if train else 0
@@ -477,13 +492,19 @@ class Engine:
                      pre=A.pre[li] if train else None, act=A.act[li], out=xout)
             if prune and i == cfg.depth - 1:
                 Rc = self._cls_rows(A, n, xin)
-                ch.attn_fwd(b, R, cls=Rc, split_q=self.PRUNE_Q)
+                ch.attn_fwd(b, R, cls=Rc, split_q=self.PRUNE_Q, ln_done=ln_done)
                 ch.mlp_fwd(b, Rc, train)
                 if self.capture is not None:
                     self.capture("fwd_cls", train, i, xin[:M], A.c_xout[:n])
                 break
-            ch.attn_fwd(b, R)
-            ch.mlp_fwd(b, R, train, fused=fused, label="fc1_fwd" if train else "fc1_fwd_weak")
+            ch.attn_fwd(b, R, ln_done=ln_done)
+            next_ln = None
+            if fc2_ln and i + 1 < cfg.depth:
+                nb, ni = f"blocks.{i + 1}.", i + 1 if train else 0
+                next_ln = (self.view(flat, nb + "norm1.weight"), self.view(flat, nb + "norm1.bias"), A.h1[ni],
+                           A.mean1[ni], A.rstd1[ni])
+            ch.mlp_fwd(b, R, train, fused=fused, label="fc1_fwd" if train else "fc1_fwd_weak", next_ln=next_ln)
+            ln_done = next_ln is not None
             if self.capture is not None:
                 self.capture("fwd", train, i, xin[:M], xout[:M])
         xl = A.x[cfg.depth] if train else A.x[cfg.depth & 1]

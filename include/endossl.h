@@ -49,6 +49,16 @@ int es_gemm_nt(int epi, const void* A, int lda, const void* B, int ldb, const fl
 int es_gemm_nt_resid_ln(const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc,
                         const float* aux, int ldaux, const float* gamma, const float* beta, void* h, int ldh,
                         float* mean, float* rstd, int M, int N, int K, float eps, hipStream_t stream);
+/* The MLP's fc2, its residual add and the next block's LayerNorm 1 in one launch (N = 384, K a multiple of 64):
+ * x = A B^T + bias + aux (fp32, into C), h = LayerNorm(x; gamma, beta) (bf16) with the per-row mean / rstd the
+ * LayerNorm backward reads -- bit-identical to es_gemm_nt(epi 2) followed by es_layernorm_fwd.  A bf16 [M, lda],
+ * B bf16 [384, ldb], x fp32 [M, ldc], aux fp32 [M, ldaux], h bf16 [M, ldh]; bias nullable.  Replaces
+ * code/models/conformer.py:70-71 (x + mlp(norm2(x))) and the next block's norm1 (:65).  ES_BAD_SHAPE for other N,
+ * K % 64 != 0, M <= 0, a row stride below its width or misaligned (lda, ldb % 8; ldc, ldaux, ldh % 2);
+ * ES_BAD_ARG for a null or misaligned operand (A, B, gamma, beta, bias 16-B; C, aux 8-B; h, mean, rstd 4-B). */
+int es_gemm_nt_ln(const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc,
+                  const float* aux, int ldaux, const float* gamma, const float* beta, void* h, int ldh, float* mean,
+                  float* rstd, int M, int N, int K, float eps, hipStream_t stream);
 /* tuning knob: NT kernel family (-1 = per-shape default; 0, 1, 2, 5, 6, 10, 11 = fixed tilings, see gemm.hip;
  * 12 = the weight-stationary K = 384 kernel where it applies -- epi 0 / 1 / 4 / 6 / 7, K == 384, N a multiple
  * of 384 up to 3072 -- and the per-shape rules elsewhere; opt-in, bit-identical to the tilings);
