@@ -10,6 +10,8 @@
 //      d/d l[i][c] = grad_scale * (w[y_i] + eps * p_i[y_i]) * (p_i[c] - [c == y_i])
 //  es_triplet_fwd_bwd         code/loss.py:170-190 (TripletLoss, alpha = 0.7) on z = [anchors; positives; negatives]
 //  es_softmax_predict         code/supervised.py:258-266 (inference: argmax, max probability, thresholded label)
+//  es_margin_softmax_fwd_bwd  code/loss.py:228-266 (AngularPenaltySMLoss: normalise, fc, margin, softmax) with
+//      d/dx, d/dW, d/db -- its own two kernels, described where they stand
 // The logits are tiny ([448,23] / [64,23]); one workgroup handles all rows, staging each row's
 // logits in registers, and emits int32 pseudo-labels, the uint8 mask, per-row losses and the two
 // means -- no host sync and no intermediate tensors.
@@ -252,6 +254,177 @@ __global__ __launch_bounds__(256) void softmax_predict_kernel(const float* __res
   }
 }
 
+// AngularPenaltySMLoss (code/loss.py:228-266), value and gradient, in two launches on one stream.
+//  margin_rows_kernel    one workgroup of 4 waves per row i:
+//      x^ = x / max(|x|, 1e-12) into LDS; z_c = x^ . W_c (+ b_c), a wave per class (lanes stride the columns,
+//      wave sum); wave 0, lane c: v_c = num(t) at the target, s z_c elsewhere, lse by max subtraction,
+//      g_c = d(-grad_scale w m L_i)/d z_c into the workspace; then every thread, for its columns,
+//      dx^ = sum_c g_c W_c (class order) and dx through the normalisation.
+//  margin_reduce_kernel  dW[c] = sum_i g[i][c] x^_i, a thread per (class, 4 columns), rows in order; db and the
+//      loss sum by a wave each (lane l takes rows l, l + 64, ..., then the wave sum).
+// No atomics, every sum in a fixed order: the same bits on every launch.
+constexpr int MARGIN_THREADS = 256;
+constexpr int MARGIN_MAXF = 2048;
+enum { MARGIN_COSFACE = 0, MARGIN_ARCFACE = 1, MARGIN_SPHEREFACE = 2, MARGIN_ACLOSS = 3 };
+
+struct MarginParams {
+  int kind;
+  float s, m, eps, lo, hi;  // lo, hi: the clamp range of the target cosine, -1 + eps and 1 - eps in fp32
+  float cos_m, sin_m;  // arcface: cos(theta + m) = t cos m - sqrt(1 - t^2) sin m
+  float sig1, inv_k;   // acloss g_theta: (1 + e^(-pi/2k)) / (1 - e^(-pi/2k)), 1 / k
+  float grad_scale;
+};
+
+// num(t) and d num / d t; the clamp passes no gradient outside [lo, hi] (torch.clamp's backward)
+__device__ __forceinline__ void margin_numerator(const MarginParams& P, float t, float& num, float& dnum) {
+  if (P.kind == MARGIN_COSFACE) {
+    num = P.s * (t - P.m);
+    dnum = P.s;
+    return;
+  }
+  const bool inside = t >= P.lo && t <= P.hi;
+  const float tc = fminf(fmaxf(t, P.lo), P.hi);
+  // 1 -+ tc: exact differences inside the range; at a clamped end the distance to +-1 is eps itself, which
+  // fp32 cannot carry in tc (1 - 1e-7 rounds to 1 - 1.19e-7).  sq = sin(acos(tc)) > 0, theta = acos(tc)
+  const float om = inside ? 1.0f - tc : (t > P.hi ? P.eps : 2.0f - P.eps);
+  const float op = inside ? 1.0f + tc : (t > P.hi ? 2.0f - P.eps : P.eps);
+  const float sq = sqrtf(om * op);
+  float d;
+  if (P.kind == MARGIN_ARCFACE) {
+    num = P.s * (tc * P.cos_m - sq * P.sin_m);
+    d = P.s * (P.cos_m + tc * P.sin_m / sq);
+  } else if (P.kind == MARGIN_SPHEREFACE) {
+    const float th = P.m * atan2f(sq, tc);
+    num = P.s * cosf(th);
+    d = P.s * P.m * sinf(th) / sq;
+  } else {  // acloss: s g_theta(acos(tc) + m), g_theta(a) = sig1 (1 - e) / (1 + e), e = exp((a - pi/2) / k)
+    const float e = expf((atan2f(sq, tc) + P.m - 1.57079632679489662f) * P.inv_k);
+    num = P.s * P.sig1 * (1.0f - e) / (1.0f + e);
+    d = P.s * P.sig1 * 2.0f * e * P.inv_k / ((1.0f + e) * (1.0f + e) * sq);
+  }
+  dnum = inside ? d : 0.f;
+}
+
+__global__ __launch_bounds__(MARGIN_THREADS) void margin_rows_kernel(
+    const float* __restrict__ x, int ldx, const float* __restrict__ W, const float* __restrict__ b,
+    const int64_t* __restrict__ y, const float* __restrict__ cw, const float* __restrict__ mask, int F, int C,
+    MarginParams P, float* __restrict__ dx, int lddx, float* __restrict__ G, float* __restrict__ inv_norm,
+    float* __restrict__ ws_loss, float* __restrict__ row_loss) {
+  __shared__ __attribute__((aligned(16))) float xs[MARGIN_MAXF];
+  __shared__ float zs[MAXC], gs[MAXC], red[16];
+  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int F4 = F >> 2;
+  const f32x4* xr = (const f32x4*)(x + (size_t)i * ldx);
+  float ss = 0.f;
+  for (int k = tid; k < F4; k += MARGIN_THREADS) {
+    const f32x4 v = xr[k];
+    ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+  }
+  const float nrm = sqrtf(block_sum(ss, red));
+  const float inv = 1.0f / fmaxf(nrm, 1e-12f);
+  for (int k = tid; k < F4; k += MARGIN_THREADS) ((f32x4*)xs)[k] = xr[k] * inv;
+  __syncthreads();
+  for (int c = w; c < C; c += MARGIN_THREADS / 64) {
+    const f32x4* wr = (const f32x4*)(W + (size_t)c * F);
+    float acc = 0.f;
+    for (int k = lane; k < F4; k += 64) {
+      const f32x4 a = ((const f32x4*)xs)[k], q = wr[k];
+      acc = fmaf(a[0], q[0], acc);
+      acc = fmaf(a[1], q[1], acc);
+      acc = fmaf(a[2], q[2], acc);
+      acc = fmaf(a[3], q[3], acc);
+    }
+    acc = warp_sum(acc);
+    if (lane == 0) zs[c] = acc + (b ? b[c] : 0.f);
+  }
+  __syncthreads();
+  if (w == 0) {
+    const int64_t y64 = y[i];
+    const bool valid = y64 >= 0 && y64 < C;
+    const int yi = valid ? (int)y64 : -1;
+    const float wm = (valid && cw ? cw[yi] : 1.f) * (mask ? mask[i] : 1.f);
+    float num = 0.f, dnum = 0.f;
+    margin_numerator(P, zs[valid ? yi : 0], num, dnum);
+    const bool tgt = lane == yi;
+    const float v = lane < C ? (tgt ? num : P.s * zs[lane]) : -INFINITY;
+    const float mx = warp_max(v);
+    const float e = lane < C ? expf(v - mx) : 0.f;
+    const float se = warp_sum(e);
+    const float rest = warp_sum(tgt ? 0.f : e);  // 1 - p_target = rest / se, without the cancellation
+    const float lse = mx + logf(se);
+    const float coef = P.grad_scale * wm;
+    float g = tgt ? -coef * (rest / se) * dnum : coef * P.s * (e / se);
+    float rl = wm * (lse - num);
+    if (!valid) {  // invalid target: NaN loss, no gradient, no out-of-range read
+      g = 0.f;
+      rl = __int_as_float(0x7fc00000);
+    }
+    if (lane < C) {
+      gs[lane] = g;
+      G[(size_t)i * C + lane] = g;
+    }
+    if (lane == 0) {
+      inv_norm[i] = inv;
+      ws_loss[i] = rl;
+      if (row_loss) row_loss[i] = rl;
+    }
+  }
+  __syncthreads();
+  // at most MARGIN_MAXF / 4 / MARGIN_THREADS = 2 column groups per thread
+  f32x4 acc[2];
+  float dot = 0.f;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int k = tid + j * MARGIN_THREADS;
+    acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (k < F4) {
+      for (int c = 0; c < C; ++c) acc[j] += ((const f32x4*)(W + (size_t)c * F))[k] * gs[c];
+      const f32x4 a = ((const f32x4*)xs)[k];
+      dot += a[0] * acc[j][0] + a[1] * acc[j][1] + a[2] * acc[j][2] + a[3] * acc[j][3];
+    }
+  }
+  dot = block_sum(dot, red);
+  // F.normalize's backward: through x / |x| where |x| >= 1e-12, else through x / 1e-12 alone
+  const float proj = nrm >= 1e-12f ? dot : 0.f;
+  f32x4* dr = (f32x4*)(dx + (size_t)i * lddx);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int k = tid + j * MARGIN_THREADS;
+    if (k < F4) dr[k] = (acc[j] - ((const f32x4*)xs)[k] * proj) * inv;
+  }
+}
+
+__global__ __launch_bounds__(64) void margin_reduce_kernel(const float* __restrict__ x, int ldx,
+                                                           const float* __restrict__ G,
+                                                           const float* __restrict__ inv_norm,
+                                                           const float* __restrict__ ws_loss, int n, int F, int C,
+                                                           float grad_scale, float* __restrict__ dW,
+                                                           float* __restrict__ db, float* __restrict__ out) {
+  const int c = blockIdx.y, lane = threadIdx.x;
+  const int F4 = F >> 2, k = blockIdx.x * 64 + lane;
+  if (k < F4) {
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int i = 0; i < n; ++i)
+      acc += ((const f32x4*)(x + (size_t)i * ldx))[k] * (G[(size_t)i * C + c] * inv_norm[i]);
+    ((f32x4*)(dW + (size_t)c * F))[k] = acc;
+  }
+  if (blockIdx.x == 0) {
+    if (db) {
+      float sb = 0.f;
+      for (int i = lane; i < n; i += 64) sb += G[(size_t)i * C + c];
+      sb = warp_sum(sb);
+      if (lane == 0) db[c] = sb;
+    }
+    if (c == 0) {
+      float sl = 0.f;
+      for (int i = lane; i < n; i += 64) sl += ws_loss[i];
+      sl = warp_sum(sl);
+      if (lane == 0) out[0] = grad_scale * sl;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -316,6 +489,48 @@ int es_triplet_fwd_bwd(const float* z, int ldz, int bs, int L, float alpha, floa
   if (bs < 1 || bs > 0x7fffffff / 3 || L < 1 || L > 2048 || ldz < L || lddz < L) return ES_BAD_SHAPE;
   if (!z || !dz || !out) return ES_BAD_ARG;
   hipLaunchKernelGGL(triplet_kernel, 1, TRIPLET_THREADS, 0, stream, z, ldz, bs, L, alpha, grad_scale, dz, lddz, out);
+  return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
+}
+
+// workspace of es_margin_softmax_fwd_bwd in floats: g [n, C], 1 / max(|x_i|, 1e-12) [n], row losses [n]
+size_t es_margin_softmax_workspace(int n, int C) {
+  if (n < 1 || C < 1 || C > MAXC) return 0;
+  return (size_t)n * (size_t)(C + 2);
+}
+
+// AngularPenaltySMLoss.forward and its gradient (the header states the semantics).  Every check runs before the
+// first launch; a refused call writes nothing.
+int es_margin_softmax_fwd_bwd(const float* x, int ldx, const float* W, const float* bias, const int64_t* targets,
+                              const float* class_weights, const float* mask, int n, int F, int C, int kind, float s,
+                              float m, float eps, float grad_scale, float* dx, int lddx, float* dW, float* db,
+                              float* out, float* row_loss, float* workspace, hipStream_t stream) {
+  if (n < 1 || C < 1 || C > MAXC || F < 4 || F > MARGIN_MAXF || (F & 3) || ldx < F || lddx < F || (ldx & 3) ||
+      (lddx & 3))
+    return ES_BAD_ARG;
+  if (kind < MARGIN_COSFACE || kind > MARGIN_ACLOSS || !(eps > 0.f && eps < 1.f)) return ES_BAD_ARG;
+  if (!x || !W || !targets || !dx || !dW || !out || !workspace) return ES_BAD_ARG;
+  if (((uintptr_t)x | (uintptr_t)W | (uintptr_t)dx | (uintptr_t)dW) & 15) return ES_BAD_ARG;
+  if (((uintptr_t)workspace | (uintptr_t)out) & 3) return ES_BAD_ARG;
+  const double k = 0.3, q = exp(-M_PI / 2.0 / k);  // g_theta's k (code/loss.py:262)
+  MarginParams P;
+  P.kind = kind;
+  P.s = s;
+  P.m = m;
+  P.eps = eps;
+  P.lo = (float)(-1.0 + (double)eps);
+  P.hi = (float)(1.0 - (double)eps);
+  P.cos_m = (float)cos((double)m);
+  P.sin_m = (float)sin((double)m);
+  P.sig1 = (float)((1.0 + q) / (1.0 - q));
+  P.inv_k = (float)(1.0 / k);
+  P.grad_scale = grad_scale;
+  float* G = workspace;
+  float* inv_norm = G + (size_t)n * C;
+  float* ws_loss = inv_norm + n;
+  hipLaunchKernelGGL(margin_rows_kernel, n, MARGIN_THREADS, 0, stream, x, ldx, W, bias, targets, class_weights, mask,
+                     F, C, P, dx, lddx, G, inv_norm, ws_loss, row_loss);
+  hipLaunchKernelGGL(margin_reduce_kernel, dim3((F / 4 + 63) / 64, C), 64, 0, stream, x, ldx, G, inv_norm, ws_loss, n,
+                     F, C, grad_scale, dW, db, out);
   return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
 }
 

@@ -11,14 +11,17 @@ triplet mode (MODEL.IS_TRIPLET without TRAIN.IS_SSL, :198-200) gets the same mod
 default 256-d embedding.
 For 'conformer' it returns the native Conformer-Ti of code/build.py:135-142 (patch 16,
 channel_ratio 1, embed 384, depth 12, 6 heads, qkv_bias; conformer.NativeConformer, forward ->
-(conv_logits, trans_logits)) -- SemiFormer's backbone.  CNN / Swin backbones are outside the
+(conv_logits, trans_logits)) -- SemiFormer's backbone.  With MODEL.MARGIN set (code/build.py:173-174, checked
+first) `resnet18` gives resnet.ModelMargin, the ResNet-18 with a bias-free fc that the angular-margin step reads;
+a margin with any other backbone raises (ModelMargin needs `.fc`) unless IS_TRIPLET is set too, which the trainer
+tests first and which keeps building the plain backbone.  Other CNN / Swin backbones are outside the
 hot path.
 """
 import torch
 
 from .comatch_model import NativeViTEmb
 from .conformer import ConformerConfig, NativeConformer
-from .resnet import NativeResNet, ResNetConfig
+from .resnet import ModelMargin, NativeResNet, ResNetConfig
 from .vit import VIT_CONFIGS, NativeViT, ViTConfig
 
 TRIPLET_LOW_DIM = 256  # ModelwEmb's default low_dim (code/models/custom_model.py:147)
@@ -26,6 +29,15 @@ TRIPLET_LOW_DIM = 256  # ModelwEmb's default low_dim (code/models/custom_model.p
 def build_model(config, is_pathology=True, seed=0):
     name = config.MODEL.NAME
     C = int(config.MODEL.NUM_CLASSES)
+    if name != "conformer" and str(getattr(config.MODEL, "MARGIN", "None")) != "None":
+        # code/build.py:173-174: checked before IS_SSL / IS_TRIPLET / PRE_TRAIN_PATH, none of which is read here
+        if name == "resnet18":
+            return ModelMargin(ResNetConfig(num_classes=C, fc_bias=False), seed=seed)
+        # With IS_TRIPLET also set the trainer never reads the margin (code/supervised.py:84 tests the triplet
+        # first): such a config keeps building the plain backbone below, as before the margin mode existed.
+        if not getattr(config.MODEL, "IS_TRIPLET", False):
+            raise NotImplementedError(f"MODEL.MARGIN with backbone {name!r}: ModelMargin needs a backbone with a .fc "
+                                      "classifier (code/models/custom_model.py:129); the native one is resnet18")
     if name == "conformer":
         img = int(config.DATA.IMG_SIZE) if "IMG_SIZE" in config.DATA else 224
         model = NativeConformer(ConformerConfig(img_size=img, patch=16, channel_ratio=1, embed_dim=384, depth=12,

@@ -13,6 +13,9 @@ all but the 3-channel stem; `set_conv_precision("fp32")` for parity), BatchNorm 
 and ReLU fused into its apply pass, SyncBatchNorm at N > 1 (as the Conformer).  With the bf16 convs
 the activation and gradient maps after the stem's max-pool are bf16 (map_bf16; the stem and BatchNorm
 statistics stay fp32, ENDOSSL_MAP_BF16=0 keeps fp32 maps): every conv after the stem is bf16-eligible.
+
+`ModelMargin` (code/models/custom_model.py:122-134) is the same network with a bias-free fc and a `backbone(x)`
+that stops at the pooled features: the model of the angular-margin supervised mode (MODEL.MARGIN).
 """
 import math
 
@@ -20,16 +23,18 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .conformer import (BN_EPS_STEM, CONV_BF16, GRAD_SINKS, MAP_BF16, NativeConformer, _ConvHeadFn, _GradSink, _Map,
-                        _map_dtype, _MaxPoolFn, _join_queued, _rup, bn, bn_conv, conv)
+from ._lib import call, ptr
+from .conformer import (BN_EPS_STEM, CONV_BF16, GRAD_SINKS, MAP_BF16, NativeConformer, _ConvHeadFn, _fl, _GradSink, _Map,
+                        _map_dtype, _MaxPoolFn, _join_queued, _own, _rup, _s, bn, bn_conv, conv)
 
 BN_EPS = 1e-5  # timm BasicBlock norm_layer = nn.BatchNorm2d (default eps)
 
 
 class ResNetConfig:
-    def __init__(self, layers=(2, 2, 2, 2), num_classes=23, img_size=224, widths=(64, 128, 256, 512)):
+    def __init__(self, layers=(2, 2, 2, 2), num_classes=23, img_size=224, widths=(64, 128, 256, 512), fc_bias=True):
         self.layers, self.widths = tuple(layers), tuple(widths)
         self.num_classes, self.img_size = num_classes, img_size
+        self.fc_bias = bool(fc_bias)  # False: ModelMargin's nn.Linear(512, C, bias=False)
 
     def blocks(self):
         """(prefix, inplanes, planes, stride, downsample) per BasicBlock in state_dict order."""
@@ -56,13 +61,16 @@ def resnet_layout(cfg):
         if ds:
             out += [(pre + "downsample.0.weight", (w, inp, 1, 1), "p")] + _bn_entries(pre + "downsample.1.", w)
     C = cfg.num_classes
-    out += [("fc.weight", (C, cfg.widths[-1]), "p"), ("fc.bias", (C,), "p")]
+    out += [("fc.weight", (C, cfg.widths[-1]), "p")]
+    if getattr(cfg, "fc_bias", True):
+        out += [("fc.bias", (C,), "p")]
     return out
 
 
 def init_resnet_(flat, layout, offs, generator=None):
     """timm ResNet.init_weights: kaiming-normal (fan_out, ReLU) convs, BatchNorm weight 1 / bias 0,
     fc as nn.Linear's default (uniform +-1/sqrt(fan_in) for weight and bias)."""
+    fan_in = next(shape[1] for name, shape, _ in layout if name == "fc.weight")
     for name, shape, kind in layout:
         if kind != "p":
             continue
@@ -71,7 +79,7 @@ def init_resnet_(flat, layout, offs, generator=None):
             std = math.sqrt(2.0 / (shape[0] * shape[2] * shape[3]))
             t.normal_(0.0, std, generator=generator)
         elif name.startswith("fc."):
-            bound = 1.0 / math.sqrt(layout[-2][1][1])
+            bound = 1.0 / math.sqrt(fan_in)
             t.uniform_(-bound, bound, generator=generator)
         elif name.endswith("weight"):
             t.fill_(1.0)
@@ -132,10 +140,11 @@ class NativeResNet(NativeConformer):
             return bn(self, h, pre + "bn2.", eps=BN_EPS, relu=True, res=sc)
         return bn(self, h, pre + "bn2.", eps=BN_EPS, relu=True, res=x, res_sink=sink)
 
-    def forward(self, x):
+    def _trunk(self, x):
+        """Images -> (the last stage's NHWC map, the head's tape anchor under a frozen trunk)."""
         cfg = self.cfg
         if not self.flat.is_cuda:
-            raise _lib.EndosslCallError("NativeResNet runs on the MI355X only: move it to a cuda device first")
+            raise _lib.EndosslCallError(f"{type(self).__name__} runs on the MI355X only: move it to a cuda device first")
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError(f"expected [n, 3, H, W] images, got {tuple(x.shape)}")
         _join_queued.clear()
@@ -151,5 +160,107 @@ class NativeResNet(NativeConformer):
         h = _MaxPoolFn.apply(bn(self, h, "bn1.", eps=BN_EPS_STEM, relu=True), 3, 2, 1, _map_dtype(self))
         for pre, inp, planes, stride, ds in cfg.blocks():
             h = self._block(h, pre, inp, planes, stride, ds)
-        head_anchor = self._anchor if (on_tape and frozen) else None
+        return h, (self._anchor if (on_tape and frozen) else None)
+
+    def forward(self, x):
+        h, head_anchor = self._trunk(x)
         return _ConvHeadFn.apply(h, self, head_anchor, "fc.")
+
+
+class _GlobalPoolFn(torch.autograd.Function):
+    """AdaptiveAvgPool2d(1) + flatten: NHWC map (fp32 or bf16) -> [N, C] fp32 features."""
+
+    @staticmethod
+    def forward(ctx, x):
+        N, H, W, C = x.shape
+        if H != W:
+            raise ValueError(f"the global pool expects square maps, got {H}x{W}")
+        pooled = torch.empty(N, C, device=x.device)
+        call("es_avgpool2d_fwd_ex", ptr(x.contiguous()), N, H, W, C, H, ptr(pooled), _fl(x), _s())
+        ctx.geom, ctx.dt = (N, H, W, C), x.dtype
+        return pooled
+
+    @staticmethod
+    def backward(ctx, dp):
+        _own(dp)
+        N, H, W, C = ctx.geom
+        dp = dp.float().contiguous()
+        dx = torch.empty(N, H, W, C, dtype=ctx.dt, device=dp.device)
+        call("es_avgpool2d_bwd_ex", ptr(dp), N, H, W, C, H, ptr(dx), 0, _fl(dx) << 1, _s())
+        return dx
+
+
+class _LinearNoBiasFn(torch.autograd.Function):
+    """fts [N, K] -> fts fc.weight^T; the weight gradient goes to the flat gradient (overwritten)."""
+
+    @staticmethod
+    def forward(ctx, fts, m, anchor=None):
+        N, K = fts.shape
+        ncls = m.cfg.num_classes
+        fts = fts.contiguous()
+        logits = torch.empty(N, ncls, device=fts.device)
+        call("es_dense_fwd", ptr(fts), K, ptr(m.pview("fc.weight")), None, ptr(logits), ncls, N, K, ncls, 0, 0.0, None,
+             1.0, _s())
+        ctx.save_for_backward(fts)
+        ctx.m = m
+        return logits
+
+    @staticmethod
+    def backward(ctx, dl):
+        _own(dl)
+        (fts,) = ctx.saved_tensors
+        m = ctx.m
+        N, K = fts.shape
+        ncls = m.cfg.num_classes
+        dl = dl.contiguous()
+        dfts = torch.empty(N, K, device=dl.device)
+        ws = torch.empty(_lib.load().es_dense_bwd_workspace(N, ncls), device=dl.device)
+        call("es_dense_bwd", ptr(dl), ncls, None, 0, 0, 0.0, None, 1.0, ptr(fts), K, ptr(m.pview("fc.weight")),
+             ptr(dfts), K, 0, ptr(m.gview("fc.weight")), None, N, K, ncls, ptr(ws), _s())
+        return (dfts if ctx.needs_input_grad[0] else None), None, None
+
+
+class ModelMargin(NativeResNet):
+    """ModelMargin over resnet18 (code/models/custom_model.py:122-134): the ResNet-18 with a bias-free fc, for
+    the angular-margin losses (loss.AngularPenaltySMLoss reads `fc.weight`, code/supervised.py:117-119).
+
+      model(x)            plain logits fc(pool(trunk(x))), no normalisation (evaluate_one / inference)
+      model.backbone(x)   the pooled [n, 512] features, on the autograd tape in training mode
+      model.fc            the classifier module; `.weight` [C, 512] is a view of the flat buffer
+
+    state_dict: the reference's `model.*` keys (timm's resnet18 names under `model.`, `model.fc.weight`, no
+    bias) followed by its `fc.weight` alias of the same tensor.  The reference also lists every trunk tensor a
+    second time as `backbone.N.*` (nn.Sequential over timm's children): loading skips those keys, and they are
+    not written -- timm is absent, so the index map N is unpinned."""
+
+    def __init__(self, cfg=None, seed=None, **kw):
+        cfg = cfg if cfg is not None else ResNetConfig(fc_bias=False, **kw)
+        if cfg.fc_bias:
+            raise ValueError("ModelMargin's fc has no bias: build its config with fc_bias=False")
+        super().__init__(cfg, seed=seed)
+
+    def backbone(self, x):
+        h, _ = self._trunk(x)
+        return _GlobalPoolFn.apply(h)
+
+    def forward(self, x):
+        h, head_anchor = self._trunk(x)
+        return _LinearNoBiasFn.apply(_GlobalPoolFn.apply(h), self, head_anchor)
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        if args:
+            raise TypeError("ModelMargin.state_dict takes destination / prefix / keep_vars by keyword")
+        own = super().state_dict(prefix="", keep_vars=keep_vars)
+        out = type(own)() if destination is None else destination
+        for k, v in own.items():
+            out[prefix + "model." + k] = v
+        out[prefix + "fc.weight"] = own["fc.weight"]
+        return out
+
+    def load_state_dict(self, state_dict, strict=True):
+        own = {}
+        for k, v in state_dict.items():
+            if k.startswith("backbone."):
+                continue
+            own[k[len("model."):] if k.startswith("model.") else k] = v
+        return super().load_state_dict(own, strict=strict)

@@ -21,8 +21,19 @@ a direct launch sequence, no autograd:
   opt    as above
 
 `test_one` (:198-236) and `inference` (:238-268, the pseudo-labelling pass; es_softmax_predict) take
-tuple-returning and plain-logit models.  The margin (AngularPenaltySMLoss) and mixup paths are out of the
-§8 scope and raise NotImplementedError.
+tuple-returning and plain-logit models.
+
+The margin mode (MODEL.MARGIN in cosface / arcface / sphereface / acloss, :117-119) runs on resnet.ModelMargin:
+
+  fwd    fts = model.backbone(images)                         the pooled [n, 512] features
+  loss   AngularPenaltySMLoss(fts, y, model.fc, class_weights) with d/dfts and d/dfc.weight in one call
+         (es_margin_softmax_fwd_bwd; the weight gradient goes straight into the flat gradient)
+  bwd    autograd from dfts through the trunk
+  opt    as above
+
+step() returns {"loss", "fts"} there.  With IS_TRIPLET also set the triplet step runs, as in the reference (:84).
+The mixup path is dead code in the reference (dataset.py always returns mixup_fn = None) and raises
+NotImplementedError.
 """
 import os
 from datetime import date, datetime
@@ -34,11 +45,16 @@ from . import _lib, dist
 from ._lib import call, ptr
 from .conformer import join_wgrad_stream
 from .ema import ModelEMA
-from .loss import weighted_ce_fwd_bwd
+from .loss import AngularPenaltySMLoss, margin_softmax_fwd_bwd, weighted_ce_fwd_bwd
 from .lr_scheduler import build_scheduler
 from .optimizer import build_optimizer
 from .throttle import StepThrottle
 from .utils import AverageMeter, balanced_class_weights, calculate_metrics
+
+
+class MarginModelError(ValueError, NotImplementedError):
+    """MODEL.MARGIN with a model the margin step cannot run on (no `.backbone` / `.fc`): a wrong value for this
+    model, and -- as callers of the earlier, margin-less trainer caught it -- not implemented for it."""
 
 
 class SupLearning:
@@ -64,10 +80,17 @@ class SupLearning:
     def get_config(self, config):
         self.config = config
         print('Training mode: Supervised Learning')
-        if str(getattr(config.MODEL, "MARGIN", "None")) != "None":
-            raise NotImplementedError("the angular-margin losses are outside the native step's scope")
+        margin = str(getattr(config.MODEL, "MARGIN", "None")) != "None"
         self.is_triplet = bool(getattr(config.MODEL, "IS_TRIPLET", False))
-        if self.is_triplet and getattr(getattr(self.model, "cfg", None), "head", None) != "emb":
+        emb = getattr(getattr(self.model, "cfg", None), "head", None) == "emb"
+        # code/supervised.py:84: IS_TRIPLET is tested first, so a margin config with it runs the triplet step
+        self.is_margin = margin and not self.is_triplet
+        if margin and not (self.is_triplet and emb) and not (hasattr(self.model, "backbone")
+                                                             and hasattr(self.model, "fc")):
+            raise MarginModelError("MODEL.MARGIN needs a model with .backbone and .fc (code/supervised.py:118-119): "
+                                   "build it with build_model(config) with MODEL.MARGIN set (resnet18)")
+        self.loss_fc = AngularPenaltySMLoss(config, device=self.device) if margin else None
+        if self.is_triplet and not emb:
             raise ValueError("MODEL.IS_TRIPLET needs the embedding-head model (logits, fts, z): build it with "
                              "build_model(config) with MODEL.IS_TRIPLET set and TRAIN.IS_SSL off")
         self.triplet_alpha = 0.7  # TripletLoss(alpha=0.7) (code/supervised.py:60)
@@ -181,6 +204,35 @@ class SupLearning:
         return {"loss": stats[5], "ce": stats[0], "triplet": stats[1], "d_ap": stats[2], "d_an": stats[3],
                 "active": stats[4], "logits": logits, "fts": fts, "z": z}
 
+    def _step_margin(self, batch):
+        """code/supervised.py:117-119 (MODEL.MARGIN set): fts = model.backbone(images); the margin loss on
+        (fts, y, model.fc, class weights) -- value, d/dfts and d/dfc.weight in one es_margin_softmax_fwd_bwd
+        call, the weight gradient written straight into the flat gradient; autograd from dfts through the
+        trunk.  Eager (not part of the graph replay), no host sync.  Data-parallel: each rank's plain mean over
+        its equal shard (grad_scale 1 / n_local), so the gradient average over ranks is the global mean's."""
+        images, targets = batch
+        m, lf = self.model, self.loss_fc
+        dev = m.flat.device
+        self._inflight.wait()
+        targets = targets.to(dev, non_blocking=True).to(torch.int64).contiguous()
+        images = images.to(dev, non_blocking=True)
+        m.train()
+        fts = m.backbone(images)
+        n = int(fts.shape[0])
+        x = fts.detach()
+        stats = torch.empty(1, dtype=torch.float32, device=dev)
+        dfts = torch.empty_like(x)
+        self.optimizer.zero_grad()
+        margin_softmax_fwd_bwd(x, m.pview("fc.weight").view(m.shapes["fc.weight"]), None, targets, self.class_weights,
+                               None, lf.loss_type, lf.s, lf.m, lf.eps, 1.0 / n, dfts,
+                               m.gview("fc.weight").view(m.shapes["fc.weight"]), None, stats)
+        if fts.requires_grad:  # not under a frozen trunk (IS_FREEZE): fc.weight alone trains then
+            torch.autograd.backward([fts], [dfts])
+        join_wgrad_stream(dev)
+        dist.allreduce_mean_(stats)  # every rank logs the global mean
+        self._finish_step()
+        return {"loss": stats[0], "fts": x}
+
     def _finish_step(self):
         """Gradient all-reduce, optimizer + parameter EMA in one sweep, EMA of the BatchNorm buffers."""
         gscale = dist.allreduce_sum_(self.model.flat_grad)
@@ -193,12 +245,15 @@ class SupLearning:
         self._inflight.record()
 
     def step(self, batch, drop_keep=None):
-        """batch = (images [n, 3, H, W], targets [n]) -> {"loss", "logits"} (device tensors).
+        """batch = (images [n, 3, H, W], targets [n]) -> {"loss", "logits"} (device tensors); margin mode:
+        {"loss", "fts"}.
         Triplet mode: batch = ((anchors, poss, negs), (y_a, y_p, y_n)), each image tensor [bs, 3, H, W] ->
         {"loss", "ce", "triplet", "d_ap", "d_an", "active", "logits", "fts", "z"}; drop_keep: optional uint8
         [3 bs, D/4] Dropout keep-mask to replay (parity tests)."""
         if getattr(self, "is_triplet", False):
             return self._step_triplet(batch, drop_keep)
+        if getattr(self, "is_margin", False):
+            return self._step_margin(batch)
         images, targets = batch
         dev = self.model.flat.device
         self._inflight.wait()

@@ -330,6 +330,32 @@ int es_triplet_fwd_bwd(const float* z, int ldz, int bs, int L, float alpha, floa
 int es_softmax_predict(const float* logits, int ldl, int n, int C, float thres, int* pred, float* conf, int* label,
                        hipStream_t stream);
 
+/* ---- supervised angular-margin mode (code/supervised.py:117-119) ------------------------------- */
+/* code/loss.py:228-266 AngularPenaltySMLoss.forward and its autograd in one call.  x [n, F] fp32 (row stride
+ * ldx), W [C, F] row-major (nn.Linear's weight, NOT normalised: the reference's normalisation of it rebinds a
+ * local), bias [C] nullable, int64 targets, class weights w [C] and per-row mask [n] nullable (1 when absent):
+ *   x^_i = x_i / max(|x_i|, 1e-12);  z = x^ W^T (+ bias);  t_i = z[i][y_i];  tc = clamp(t, -1 + eps, 1 - eps)
+ *   kind 0 cosface     num_i = s (t - m)
+ *        1 arcface     num_i = s cos(acos(tc) + m)
+ *        2 sphereface  num_i = s cos(m acos(tc))
+ *        3 acloss      num_i = s g_theta(acos(tc) + m), g_theta of code/loss.py:262-266 (k = 0.3)
+ *   L_i = w[y_i] mask_i (num_i - log(exp(num_i) + sum_{j != y_i} exp(s z_ij)));  out[0] = -grad_scale sum_i L_i
+ * (pass 1/n: a plain mean, not weight-normalised).  The log-sum-exp subtracts its maximum, so the value stays
+ * finite where the reference's literal exp overflows (s z > 88).  The clamp passes no gradient outside its range:
+ * such a row's target logit gets none (kinds 1-3), and its loss uses the clamped cosine.
+ * Writes every entry of dx [n, F] (row stride lddx; through the normalisation), dW [C, F] and db [C] (nullable)
+ * -- the gradients of out[0] -- and of row_loss [n] (nullable; -L_i, not scaled).  An out-of-range target
+ * gives a NaN loss and a zero gradient row.  workspace: es_margin_softmax_workspace(n, C) floats (0 for an
+ * unsupported n / C).  No atomics, fixed summation order: repeated launches give the same bits.
+ * 1 <= C <= 64, F % 4 == 0, 4 <= F <= 2048, n >= 1, ldx / lddx >= F and % 4 == 0, x / W / dx / dW 16-byte
+ * aligned, kind in 0..3, 0 < eps < 1, x / W / targets / dx / dW / out / workspace non-null: anything else returns -2 (bad
+ * argument) before any launch, and nothing is written. */
+size_t es_margin_softmax_workspace(int n, int C);
+int es_margin_softmax_fwd_bwd(const float* x, int ldx, const float* W, const float* bias, const int64_t* targets,
+                              const float* class_weights, const float* mask, int n, int F, int C, int kind, float s,
+                              float m, float eps, float grad_scale, float* dx, int lddx, float* dW, float* db,
+                              float* out, float* row_loss, float* workspace, hipStream_t stream);
+
 /* ---- Conformer CNN branch (SemiFormer backbone, code/models/conformer.py:75-445) ---------------
  * fp32 NHWC maps with element strides; Conv2d groups = 1, weights in the reference layout
  * [Cout][Cin][kh][kw].  Replaces the reference's aten conv2d / batch_norm / max_pool2d /
