@@ -15,7 +15,7 @@
 // the SOURCE address so the fragment reads are bank-conflict free; two LDS stages; the stage for
 // step k+1 is issued before the MFMAs of step k.
 #include <algorithm>
-#include <cstdlib>
+#include <mutex>
 #include <type_traits>
 
 #include <hip/hip_ext.h>
@@ -354,14 +354,11 @@ __global__ __launch_bounds__(512, 1) void gemm_nt256_kernel(NTArgs p) {
 // vmcnt arithmetic holds for every wave.
 // OCC: waves per SIMD the register budget is sized for (launch_bounds' second argument; 4: <= 128
 // VGPRs, so two 8-wave workgroups share a CU and one's epilogue runs beside the other's main loop).
-// PROBE (measurement variants 13..15 only): 1 = operand stream alone, 2 = MFMAs alone (no DMA),
-// 3 = no epilogue (main loop only), 4 = operand stream alone without the epilogue, 5 = epilogue alone;
-// 0 = the kernel.
 // STAUX: cache-policy bits of the epilogue's C stores (0 plain, 2 nt, 16 sc1).  nt by default in every NT
 // family: isolated at the F1 shapes (r03, scripts/gemm_bench.py) the qkv forward 138 -> 122.5 us, proj
 // forward 92.6 -> 78.7, fc1 forward 254 -> 195 (256x128 tile), qkv data gradient 131 -> 107 (128x128 BK64);
 // sc1 (write-through, dropped from L2) was slower than plain.
-template <int EPI, int WM, int MF, int NF, int NST, int BKT, int OCC = 1, int PROBE = 0, int STAUX = 2>
+template <int EPI, int WM, int MF, int NF, int NST, int BKT, int OCC = 1, int STAUX = 2>
 __global__ __launch_bounds__(512, OCC) void gemm_nt_big_kernel(NTArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int WN = 8 / WM;
@@ -410,12 +407,10 @@ __global__ __launch_bounds__(512, OCC) void gemm_nt_big_kernel(NTArgs p) {
 #define BIG_ISSUE(BUF, K0)                                                        \
   {                                                                               \
     char* S_ = smem + (BUF) * STAGE;                                              \
-    if constexpr (PROBE != 2 && PROBE != 5) {                                     \
     _Pragma("unroll") for (int j = 0; j < IA; ++j) glds16(ga[j] + (K0), S_ + da[j]); \
     _Pragma("unroll") for (int j = 0; j < IBF; ++j) glds16(gb[j] + (K0), S_ + db[j]); \
     if constexpr (IBH) {                                                          \
       if (lane < 32) glds16(gb[IBF] + (K0), S_ + db[IBF]);                        \
-    }                                                                             \
     }                                                                             \
   }
 
@@ -441,7 +436,7 @@ __global__ __launch_bounds__(512, OCC) void gemm_nt_big_kernel(NTArgs p) {
     const char* As = smem + buf * STAGE;
     const char* Bs = As + TA;
 #pragma unroll
-    for (int kk = 0; kk < ((PROBE == 1 || PROBE >= 4) ? 0 : BKT / 32); ++kk) {
+    for (int kk = 0; kk < BKT / 32; ++kk) {
       bf16x8 af[MF], bfr[NF];
 #pragma unroll
       for (int j = 0; j < NF; ++j) {
@@ -463,10 +458,6 @@ __global__ __launch_bounds__(512, OCC) void gemm_nt_big_kernel(NTArgs p) {
     buf = buf + 1 == NST ? 0 : buf + 1;
   }
 #undef BIG_ISSUE
-  if constexpr (PROBE == 3 || PROBE == 4) {
-    if (acc[0][0][0] == 1.2345f) ((float*)p.C)[tid] = acc[MF - 1][NF - 1][3];  // keeps the MFMAs live
-    return;
-  }
   if constexpr (OCC >= 4) epre = epi_prefetch<EPI, NF>(p, m0 + wm * MF * 16, n0 + wn * NF * 16, lane);
   __builtin_amdgcn_s_barrier();
   staged_epilogue_g<EPI, MF, NF, STAUX>(p, smem + w * epi_wave_bytes<NF>(), acc, m0 + wm * MF * 16,
@@ -743,9 +734,7 @@ __global__ __launch_bounds__(256) void gemm_tn_grouped_kernel(const TNGroupEntry
 constexpr int TB1 = 384, TB2 = 192;
 __device__ __forceinline__ int swz384(int r, int c) { return c ^ ((((r >> 1) & 1) << 1) | (((r >> 3) & 1) << 2)); }
 
-// PROBE (measurement variants only, es_gemm_tn_ex 10..13): 1 = the operand stream alone (no transposed
-// reads, no MFMAs), 2 = the MFMAs alone on whatever the ring holds (no DMA); 0 = the kernel.
-template <int BKM, int NST, bool ASM = true, int PROBE = 0>
+template <int BKM, int NST>
 __device__ __forceinline__ void tn_big_body(const TNArgs& p, int split, int tile, char* smem) {
   constexpr int R1B = TB1 * 2, R2B = TB2 * 2;          // LDS row bytes: 768, 384
   constexpr int C1 = R1B / 16, C2 = R2B / 16;           // 16-B chunks per row: 48, 24
@@ -784,26 +773,20 @@ __device__ __forceinline__ void tn_big_body(const TNArgs& p, int split, int tile
   const char* b1 = (const char*)(p.A1 + (size_t)mbeg * p.ld1 + n1_0);
   const char* b2 = (const char*)(p.A2 + (size_t)mbeg * p.ld2 + n2_0);
   const size_t s1 = (size_t)BKM * p.ld1 * 2, s2 = (size_t)BKM * p.ld2 * 2;
-#define TNB_ISSUE(BUF, KT)                                                                       \
-  {                                                                                              \
-    char* S_ = smem + (BUF) * STAGE;                                                             \
-    const char* x1 = b1 + (size_t)(KT) * s1;                                                     \
-    const char* x2 = b2 + (size_t)(KT) * s2;                                                     \
-    if constexpr (PROBE != 2) {                                                                  \
-    _Pragma("unroll") for (int j = 0; j < F1; ++j) GLDS(x1 + o1[j], S_ + (j * 8 + w) * 1024);  \
-    _Pragma("unroll") for (int j = 0; j < F2; ++j) GLDS(x2 + o2[j], S_ + T1B + (j * 8 + w) * 1024); \
-    if constexpr (H2) {                                                                          \
-      if (lane < 32) GLDS(x2 + o2[F2], S_ + T1B + F2 * 8192 + w * 512);                          \
-    }                                                                                            \
-    }                                                                                            \
+  // the ring's DMA is inline asm (glds16_asm), so the transposed reads of the current stage are not preceded
+  // by a compiler drain of the next stage's DMA; retired by the counted waits below
+#define TNB_ISSUE(BUF, KT)                                                                            \
+  {                                                                                                   \
+    char* S_ = smem + (BUF) * STAGE;                                                                  \
+    const char* x1 = b1 + (size_t)(KT) * s1;                                                          \
+    const char* x2 = b2 + (size_t)(KT) * s2;                                                          \
+    _Pragma("unroll") for (int j = 0; j < F1; ++j) glds16_asm(x1 + o1[j], S_ + (j * 8 + w) * 1024);   \
+    _Pragma("unroll") for (int j = 0; j < F2; ++j) glds16_asm(x2 + o2[j], S_ + T1B + (j * 8 + w) * 1024); \
+    if constexpr (H2) {                                                                               \
+      if (lane < 32) glds16_asm(x2 + o2[F2], S_ + T1B + F2 * 8192 + w * 512);                         \
+    }                                                                                                 \
   }
 
-  // ASM: the ring's DMA as inline asm (glds16_asm), so the transposed reads of the current stage are
-  // not preceded by a compiler drain of the next stage's DMA; retired by the counted waits below
-  auto GLDS = [](const char* src, char* dst) {
-    if constexpr (ASM) glds16_asm(src, dst);
-    else glds16(src, dst);
-  };
   f32x4 acc[6][6], bacc[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) bacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -832,7 +815,7 @@ __device__ __forceinline__ void tn_big_body(const TNArgs& p, int split, int tile
     const char* T1 = smem + buf * STAGE;
     const char* T2 = T1 + T1B;
 #pragma unroll
-    for (int hh = 0; hh < (PROBE == 1 ? 0 : BKM / 32); ++hh) {
+    for (int hh = 0; hh < BKM / 32; ++hh) {
       const int r1 = hh * 32 + 8 * g + q, r2 = r1 + 4;
       const int off = (p4 & 1) * 8;
       bf16x8 bfr[6];
@@ -880,13 +863,13 @@ __device__ __forceinline__ void tn_big_body(const TNArgs& p, int split, int tile
   }
 }
 
-template <int BKM, int NST, bool ASM = true, int PROBE = 0>
+template <int BKM, int NST>
 __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(TNArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int ntiles = (p.N1 / TB1) * (p.N2 / TB2);
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int split = wg / ntiles;
-  tn_big_body<BKM, NST, ASM, PROBE>(p, split, wg - split * ntiles, smem);
+  tn_big_body<BKM, NST>(p, split, wg - split * ntiles, smem);
 }
 
 // ---- a Linear layer's weight gradients as ONE split-K launch on the 384 x 192 tile ----------------
@@ -918,7 +901,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_grouped_kernel(const TNBig
   const TNArgs a = t.e[e].a;
   const int local = wg - t.e[e].wg0, nt = t.e[e].ntiles;
   const int split = local / nt;
-  tn_big_body<BKM, NST, true, 0>(a, split, local - split * nt, smem);
+  tn_big_body<BKM, NST>(a, split, local - split * nt, smem);
 }
 
 // out[i] = sum_s P[s][i] for every entry of a table (the grouped launch's weight slabs and bias
@@ -1137,427 +1120,26 @@ int reduce_partials_multi(const RedPairEntry* ents, int n, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Weight-stationary NT GEMM for K = 384 (round 6, es_gemm_nt variant 12).
-//
-// Every tiled NT kernel above re-reads its operands from L2 into LDS once per output tile: a 256 x 128 tile at
-// K = 384 moves (256 + 128) x 768 B for 32 K outputs, 9 B per output, and the K = 384 GEMMs of the ViT step
-// measured their L2 -> LDS operand stream at ~14 TB/s (~23 B/clk/CU), which -- not the matrix cores -- set
-// their pace.  Here one persistent 8-wave workgroup per CU owns a 384-column group of C and
-// keeps that group's weight rows in REGISTERS for the whole launch: wave w holds W[n0 + 48 w .. + 48][0 .. 384)
-// as the MFMA A operand (3 column fragments x 12 K fragments of v_mfma_f32_16x16x32_bf16 = 144 VGPRs).  The
-// workgroup walks 32-row tiles of A; each tile is staged into LDS once by LDS-DMA (4-stage ring, 24 KiB per
-// stage, source-side XOR swizzle: chunk c of row r at chunk c ^ (r & 15), conflict-free fragment reads) and
-// consumed by all eight waves, so the L2 -> LDS stream carries 768 B per 384 outputs (2 B per output).
-//   Accumulation: each output is the same chain of 12 MFMAs in K order, with the same operand roles (weights as
-// the A operand, activations as B) as the tiled kernels, so the fp32 accumulators -- and every epilogue's
-// outputs -- are bit-identical to variants 0 / 5 / 10 (tested).
-//   Epilogue: straight from the MFMA layout, one 16-row block at a time, interleaved with the other block's
-//   MFMAs by wave role (see the step body).  An LDS-staged epilogue (whole 768-B row stretches per store,
-//   double-buffered staging tiles) was built and measured too: bit-identical, but slower (qkv forward 133.7
-//   vs 122 us direct); so was the first version, a single fp32 staging tile behind a second barrier per step
-//   (119-126 us).
-//   Work distribution: row tiles are claimed dynamically, in chunks of 2, from per-(XCD range, column group)
-//   counters (agent-scope atomics on a code-object array, one counter block per HIP stream; the last workgroup
-//   to finish resets it), three chunks ahead of use.  A static split would be wrong for this engine: the
-//   data-gradient GEMMs share the chip with the weight-gradient launches of the side stream (3/8 of the CUs for
-//   ~1 ms), so a workgroup that only gets a CU late must find the work already taken instead of extending the
-//   launch.  All ring DMA is inline asm (glds16_asm): the explicit counted vmcnt at the top of each step retires
-//   it (the count follows every VMEM op this wave issued since, in issue order: claim atomics, DMA pieces, C
-//   stores).
-//   Measured (scripts/ws_bench.py, default rules vs variant 12, us): qkv forward 108 / 123, weak qkv 91 / 100,
-//   fc1 forward 190 / 246, weak fc1 154 / 162, proj dgrad 40 / 51, fp32-out N = 384 61 / 50.  So variant 12
-//   stays opt-in: per-step stamps (PROBE 7) show a wave's step ~6.4 K cycles with ~1.9 K waiting on its ring
-//   stage and each MFMA half ~1 K, and a no-MFMA probe streams the same bytes in 67 us -- the chain of ring
-//   wait, fragment reads and MFMAs per 32-row step, not HBM, sets the pace, and one workgroup per CU (the
-//   weights fill the registers) leaves no second workgroup to cover it.
-namespace wsg {
-constexpr int R = 32;                      // output rows per step (one A tile)
-constexpr int KD = 384;                    // reduction depth
-constexpr int NG = 384;                    // output columns per workgroup (8 waves x 48)
-constexpr int ROWB = KD * 2;               // A row bytes in the ring
-constexpr int STAGE = R * ROWB;            // 24 KiB
-constexpr int NST = 4;                     // ring stages (three tiles in flight behind the current one)
-constexpr int PIECES = STAGE / 1024 / 8;   // LDS-DMA instructions per wave per stage
-constexpr int CH = 2;                      // row tiles per claimed chunk
-constexpr int QN = 8;                      // chunk-index ring (LDS)
-constexpr int SLOTS = 64, SLOT_INTS = 64;  // counter blocks (one per stream): heads [xcd * 8 + cg], [63] done
-constexpr int LDS = NST * STAGE + QN * 4 + 16 + NG * 4;  // ring, chunk ring, scratch, the column group's bias
-}  // namespace wsg
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-__device__ int g_ws_ctr[wsg::SLOTS * wsg::SLOT_INTS];
-// measurement build (PROBE 7): per-step s_memtime stamps of workgroup 0's waves 0 and 4 (endossl_ws_debug_stamps)
-constexpr int WS_DBG = 2 * 64 * 8;
-__device__ unsigned long long g_ws_dbg[WS_DBG];
-
-// A chunk claim: one lane's returning agent-scope add (the same instruction hipcc emits for
-// __hip_atomic_fetch_add(.., __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)), as inline asm so that hipcc neither
-// waits for it nor moves the result to an SGPR right away; the caller retires it with a counted vmcnt before
-// ws_publish_asm reads the result (cdna_hip_programming.md §5.7 item 1, form ii: the destination is named again
-// by the consuming statement; audited in the .s: no copy of it between the two).
-__device__ __forceinline__ void ws_claim_asm(int* head, int& ret) {
-  unsigned long long save;
-  asm volatile(
-      "s_mov_b64 %1, exec\n\t"
-      "s_mov_b64 exec, 1\n\t"
-      "s_nop 4\n\t"
-      "global_atomic_add %0, %2, %3, off sc0\n\t"
-      "s_mov_b64 exec, %1"
-      : "=&v"(ret), "=&s"(save)
-      : "v"(head), "v"(1)
-      : "memory");
-}
-// lane 0 stores the claimed chunk index to the LDS ring (the other lanes store nothing)
-__device__ __forceinline__ void ws_publish_asm(int* slot_lds, int& v, int lane) {
-  const unsigned a = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)slot_lds;
-  unsigned long long save;
-  asm volatile(
-      "s_mov_b64 %1, exec\n\t"
-      "s_mov_b64 exec, 1\n\t"
-      "s_nop 4\n\t"
-      "ds_write_b32 %2, %0\n\t"
-      "s_mov_b64 exec, %1"
-      : "+v"(v), "=&s"(save)
-      : "v"(a)
-      : "memory");
-  (void)lane;
-}
-
-// The MFMA phase of a step: 24 activation fragments (2 row blocks x 12 K steps), each feeding 3 MFMAs, read by
-// inline-asm ds_read_b128 kept WS_PF ahead (hipcc, at ~240 VGPRs, issued each read right before its MFMAs and
-// waited for it: one LDS round trip per 3 MFMAs).  Each wait names its fragment ("+v", cdna_hip_programming.md
-// §5.7 item 1 form ii) so no MFMA is scheduled above it; LDS returns in order, so lgkmcnt(reads issued after
-// fragment t) retires fragment t.  Chunk 4 kk + g of row r sits at chunk (4 kk + g) ^ r =
-// 16 (kk >> 2) + 4 ((kk & 3) ^ (r >> 2)) + (g ^ (r & 3)): four per-lane bases (kk & 3) plus constants.
-constexpr int WS_PF = 4;
-__device__ __forceinline__ void ws_ds_read(bf16x8& x, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1" : "=v"(x) : "v"(addr) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ws_lgkm_wait(bf16x8& x) {
-  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(x) : "i"(N) : "memory");
-}
-template <int T>
-__device__ __forceinline__ unsigned ws_frag_addr(const unsigned (&xb4)[4]) {
-  constexpr int kk = T % 12;
-  return xb4[kk & 3] + (T / 12) * 16 * wsg::ROWB + (kk >> 2) * 256;
-}
-template <int A, int T>
-__device__ __forceinline__ void ws_mfma_loop(f32x4 (&acc)[2][3], const bf16x8 (&wf)[3][12], const unsigned (&xb4)[4],
-                                             bf16x8 (&xs)[WS_PF]) {
-  if constexpr (T < 12) {
-    constexpr int after = (11 - T) < (WS_PF - 1) ? (11 - T) : (WS_PF - 1);
-    ws_lgkm_wait<after>(xs[T % WS_PF]);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) acc[A][j] = mfma16(wf[j][T], xs[T % WS_PF], acc[A][j]);
-    if constexpr (T + WS_PF < 12) ws_ds_read(xs[T % WS_PF], ws_frag_addr<A * 12 + T + WS_PF>(xb4));
-    ws_mfma_loop<A, T + 1>(acc, wf, xb4, xs);
-  }
-}
-// row block A (16 rows) of a step: 12 fragments x 3 MFMAs
-template <int A>
-__device__ __forceinline__ void ws_mfma_half(f32x4 (&acc)[2][3], const bf16x8 (&wf)[3][12], const unsigned (&xb4)[4]) {
-  static_assert(WS_PF == 4, "prologue reads");
-#pragma unroll
-  for (int j = 0; j < 3; ++j) acc[A][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  bf16x8 xs[WS_PF];
-  ws_ds_read(xs[0], ws_frag_addr<A * 12 + 0>(xb4));
-  ws_ds_read(xs[1], ws_frag_addr<A * 12 + 1>(xb4));
-  ws_ds_read(xs[2], ws_frag_addr<A * 12 + 2>(xb4));
-  ws_ds_read(xs[3], ws_frag_addr<A * 12 + 3>(xb4));
-  ws_mfma_loop<A, 0>(acc, wf, xb4, xs);
-}
-
-// Row chunks are split into 8 contiguous ranges, one per XCD: a workgroup claims from its own XCD's range of its
-// column group first (the column groups of one XCD then stream the same A rows, which its L2 serves to all but
-// the first), then from the next XCDs' ranges once its own is exhausted.  One lane; blocking (the prologue's claims
-// and the rare range switch at the end of a range).
-__device__ __forceinline__ int ws_range_lo(int xr, int nch) { return (xr * nch) >> 3; }
-__device__ int ws_claim_blocking(int* heads, int cg, int& xr, int& visited, int nch) {
-  while (visited < 8) {
-    const int lo = ws_range_lo(xr, nch), len = ws_range_lo(xr + 1, nch) - lo;
-    const int r = __hip_atomic_fetch_add(heads + xr * 8 + cg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (r < len) return lo + r;
-    xr = (xr + 1) & 7;
-    ++visited;
-  }
-  return nch;
-}
-
-template <int EPI>
-constexpr bool ws_epi_ok() {
-  return EPI == EPI_BF16 || EPI == EPI_GELU || EPI == EPI_GELU_ACT || EPI == EPI_GELU_D || EPI == EPI_F32;
-}
-// C stores per wave per epilogue (6 items of 4 outputs per lane; two outputs for GELU / GELU_D)
-template <int EPI>
-constexpr int ws_nstore() {
-  return (EPI == EPI_GELU || EPI == EPI_GELU_D) ? 12 : 6;
-}
-
-template <int EPI, int STAUX, int PROBE = 0>
-__global__ __launch_bounds__(512, 2) void gemm_nt_ws_kernel(NTArgs p, int ncg, int slot) {
-  using namespace wsg;
-  static_assert(ws_epi_ok<EPI>(), "epilogue");
-  static_assert(NST == 4 && CH == 2, "the claim lookahead below is written for 4 stages and 2-tile chunks");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int* const qring = (int*)(smem + NST * STAGE);
-  float* const bias_lds = (float*)(qring + QN + 4);  // the column group's bias (after 4 scratch words)
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = lane >> 4, r = lane & 15;
-  const int cg = blockIdx.x % ncg;
-  int* const ctr = g_ws_ctr + slot * SLOT_INTS;
-  const int nrt = (p.M + R - 1) / R, nch = (nrt + CH - 1) / CH;
-  const int n0 = cg * NG, nw = n0 + w * 48;
-  const bool late = w >= 4;  // waves 4..7 interleave their epilogue differently (see the step body)
-
-  // claim state (wave 0): the XCD range claimed from and how many ranges were found exhausted
-  int xr;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xr));
-  xr &= 7;
-  int visited = 0;
-  // the first three chunks: blocking claims (their latency hides behind the weight loads below)
-  if (tid == 0) {
-    if constexpr (PROBE == 5) {  // measurement: static chunks rs, rs + nrs, ... (no claims)
-      const int rs = blockIdx.x / ncg, nrs = gridDim.x / ncg;
-      qring[0] = rs; qring[1] = rs + nrs; qring[2] = rs + 2 * nrs;
-    } else {
-      qring[0] = ws_claim_blocking(ctr, cg, xr, visited, nch);
-      qring[1] = ws_claim_blocking(ctr, cg, xr, visited, nch);
-      qring[2] = ws_claim_blocking(ctr, cg, xr, visited, nch);
-      qring[QN + 0] = xr;  // (the bias follows the ring: these two words are scratch before it is written)
-      qring[QN + 1] = visited;
-    }
-  }
-  bf16x8 wf[3][12];
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-#pragma unroll
-    for (int kk = 0; kk < 12; ++kk)
-      wf[j][kk] = *(const bf16x8*)(p.B + (size_t)(nw + 16 * j + r) * p.ldb + 32 * kk + 8 * g);
-  if (tid < NG / 4)
-    *(f32x4*)(bias_lds + 4 * tid) = p.bias ? *(const f32x4*)(p.bias + n0 + 4 * tid) : f32x4{0.f, 0.f, 0.f, 0.f};
-  __syncthreads();  // weights, bias and the first claims retired (no compiler-counted load crosses into the loop)
-  if constexpr (PROBE != 5) {
-    xr = __builtin_amdgcn_readfirstlane(qring[QN + 0]);
-    visited = __builtin_amdgcn_readfirstlane(qring[QN + 1]);
-  }
-  int cur = __builtin_amdgcn_readfirstlane(qring[0]);  // chunk of the current iteration, and the two after it
-  int n1 = __builtin_amdgcn_readfirstlane(qring[1]);
-  int n2 = __builtin_amdgcn_readfirstlane(qring[2]);
-
-  // LDS-DMA source offsets of this wave's pieces within a tile (bytes from the tile's first row)
-  unsigned so[PIECES];
-#pragma unroll
-  for (int j = 0; j < PIECES; ++j) {
-    const int off = ((j * 8 + w) * 64 + lane) * 16, row = off / ROWB, c = (off % ROWB) >> 4;
-    so[j] = (unsigned)(row * p.lda * 2 + ((c ^ (row & 15)) << 4));
-  }
-  auto dma = [&](int st, int tile) {
-    const char* src = (const char*)(p.A + (size_t)tile * R * p.lda);
-#pragma unroll
-    for (int j = 0; j < PIECES; ++j) glds16_asm(src + so[j], smem + st * STAGE + (j * 8 + w) * 1024);
-  };
-  int xbase[4];  // per-lane byte offsets of the activation fragments within a stage (ws_mfma_phase)
-#pragma unroll
-  for (int k = 0; k < 4; ++k) xbase[k] = r * ROWB + ((4 * (k ^ (r >> 2)) + (g ^ (r & 3))) << 4);
-
-  // Epilogue straight from the MFMA layout: acc[a][j] holds C[m0 + 16 a + r][nw + 16 j + 4 g + 0..3] (the
-  // accumulator of D = W X^T: 4 consecutive columns of one row per lane), so each store instruction writes
-  // 16 rows x 32 (bf16) / 64 (fp32) contiguous bytes and a wave's 3 stores per row block cover 96 / 192 B;
-  // the L2 merges the eight waves' pieces of each row (plain stores: written back as whole lines).
-  constexpr bool f32out = EPI == EPI_F32;
-  const unsigned crows = (unsigned)p.M;
-  const __amdgpu_buffer_rsrc_t rc = buf_rsrc(p.C, crows * p.ldc * (f32out ? 4u : 2u));
-  const __amdgpu_buffer_rsrc_t rc2 = buf_rsrc((EPI == EPI_GELU || EPI == EPI_GELU_D) ? p.C2 : p.C, crows * p.ldc * 2u);
-  auto epilogue = [&](const f32x4 (&acc)[2][3], int tile, int a) {  // row block a of tile
-    const int m0 = tile * R;
-    f32x4 bj[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) bj[j] = *(const f32x4*)(bias_lds + w * 48 + 16 * j + 4 * g);
-    auto st8 = [&](const float* v, __amdgpu_buffer_rsrc_t rr, unsigned o) {  // 4 bf16 = 8 B
-      const bf16x4 b = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, b), rr, o, 0, STAUX);
-    };
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {  // column fragment j: 4 consecutive outputs of one row
-      const f32x4 x = acc[a][j] + bj[j];
-      float v[4] = {x[0], x[1], x[2], x[3]};
-      const int m = m0 + 16 * a + r;
-      const unsigned off = m < p.M ? (unsigned)(m * p.ldc + nw + 16 * j + 4 * g) * (f32out ? 4u : 2u) : ES_OOB;
-      if constexpr (EPI == EPI_F32) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), rc, off, 0, STAUX);
-      } else if constexpr (EPI == EPI_BF16) {
-        st8(v, rc, off);
-      } else {
-        float gg[4], dd[4];
-        gelu_and_grad_f4(v, gg, dd);
-        if constexpr (EPI == EPI_GELU_ACT) {
-          st8(gg, rc, off);
-        } else if constexpr (EPI == EPI_GELU) {
-          st8(v, rc, off);
-          st8(gg, rc2, off);
-        } else {  // EPI_GELU_D: C = gelu', C2 = gelu
-          st8(dd, rc, off);
-          st8(gg, rc2, off);
-        }
-      }
-    }
-  };
-
-  if (cur < nch) {
-    // vmcnt bookkeeping: this wave's VMEM ops since the loop started, in issue order
-    int seq = 0;
-    auto dma_valid = [&](int ch, int k) { return ch < nch && ch * CH + k < nrt; };
-    dma(0, cur * CH);  // positions 0, 1 (chunk cur) and 2 (chunk n1)
-    seq += PIECES;
-    int after_a = seq;  // seq right after the DMA of position i (retired at the top of step i), i + 1, i + 2
-    if (dma_valid(cur, 1)) {
-      dma(1, cur * CH + 1);
-      seq += PIECES;
-    }
-    int after_b = seq;
-    if (dma_valid(n1, 0)) {
-      dma(2, n1 * CH);
-      seq += PIECES;
-    }
-    int after_c = seq;
-    int st = 0;  // ring stage of the current position
-    int nstep = 0;
-    auto top = [&]() {
-      if constexpr (PROBE == 7) {
-        if (blockIdx.x == 0 && (w == 0 || w == 4) && lane == 0 && nstep < 64)
-          g_ws_dbg[((w >> 2) * 64 + nstep) * 8 + 7] = __builtin_amdgcn_s_memtime();
-      }
-      wait_vmcnt_any(seq - after_a);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();  // stage of this position landed for every wave
-    };
-    // One step: the DMA three positions ahead (tile tdma, or none), then the MFMAs and epilogue of this position
-    // (tile tcur), one 16-row block at a time.  Each SIMD holds one wave of each half of the workgroup; waves 0..3
-    // run [MFMA 0][MFMA 1][epilogue 0][epilogue 1], waves 4..7 [MFMA 0][epilogue 0][MFMA 1][epilogue 1], so
-    // each wave's epilogue (VALU, stores) runs beside its partner's MFMAs instead of both partners alternating
-    // the two in step (MI355X_MICROARCH.md, two waves per SIMD, item 9: split roles by wave number >= 4).
-    auto stamp = [&](int k) {
-      if constexpr (PROBE == 7) {
-        if (blockIdx.x == 0 && (w == 0 || w == 4) && lane == 0 && nstep < 64)
-          g_ws_dbg[((w >> 2) * 64 + nstep) * 8 + k] = __builtin_amdgcn_s_memtime();
-      }
-    };
-    auto body = [&](bool do_dma, int tdma, int tcur, auto&& tail) {
-      stamp(0);
-      int st3 = st + 3;
-      st3 = st3 >= NST ? st3 - NST : st3;
-      after_a = after_b;
-      after_b = after_c;
-      if (do_dma) {
-        dma(st3, tdma);
-        seq += PIECES;
-      }
-      after_c = seq;
-      f32x4 acc[2][3];
-      unsigned xb4[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        xb4[k] = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)(smem + st * STAGE + xbase[k]);
-      stamp(1);
-      ws_mfma_half<0>(acc, wf, xb4);
-      stamp(2);
-      if (late) {
-        epilogue(acc, tcur, 0);
-        stamp(3);
-        ws_mfma_half<1>(acc, wf, xb4);
-      } else {
-        ws_mfma_half<1>(acc, wf, xb4);
-        stamp(3);
-        epilogue(acc, tcur, 0);
-      }
-      stamp(4);
-      epilogue(acc, tcur, 1);
-      stamp(5);
-      seq += ws_nstore<EPI>();
-      tail();
-      stamp(6);
-      st = st + 1 == NST ? 0 : st + 1;
-      ++nstep;
-    };
-    // one iteration = one chunk (positions 2 lc, 2 lc + 1).  The claim for chunk lc + 3 is issued at the first
-    // position and consumed (published to LDS) at the end of the second, inside the iteration; the DMA of the
-    // first tile of chunk lc + 3 is issued at position 2 lc + 3, after the next iteration's first barrier.
-    for (int lc = 0;; ++lc) {
-      top();
-      if (lc > 0) {
-        cur = n1;
-        n1 = n2;
-        n2 = __builtin_amdgcn_readfirstlane(qring[(lc + 2) & (QN - 1)]);
-        if (cur >= nch) break;
-      }
-      const bool live = n2 < nch;
-      const bool claimer = live && w == 0;  // wave-uniform
-      int claimed = nch, after_claim = 0;
-      if (claimer) {
-        if constexpr (PROBE == 5) {
-          claimed = (int)(blockIdx.x / ncg) + (lc + 3) * (int)(gridDim.x / ncg);
-        } else {
-          ws_claim_asm(ctr + xr * 8 + cg, claimed);
-          seq += 1;
-        }
-        after_claim = seq;
-      }
-      body(dma_valid(n1, 1), n1 * CH + 1, cur * CH, [] {});
-      top();
-      if (cur * CH + 1 >= nrt) break;
-      body(dma_valid(n2, 0), n2 * CH, cur * CH + 1, [&] {
-        if (w == 0) {  // publish chunk lc + 3 (nch: none claimed) for the iterations after this one
-          int chunk = nch;
-          if (claimer) {
-            wait_vmcnt_any(seq - after_claim);
-            asm volatile("" : "+v"(claimed));  // (ordered after the wait: the claim's data is in lane 0)
-            const int raw = __builtin_amdgcn_readfirstlane(claimed);
-            if constexpr (PROBE == 5) {
-              chunk = raw;
-            } else {
-              const int lo = ws_range_lo(xr, nch), len = ws_range_lo(xr + 1, nch) - lo;
-              if (raw < len) {
-                chunk = lo + raw;
-              } else {  // this XCD's range is exhausted: the next ones (blocking; once per range at its end)
-                xr = (xr + 1) & 7;
-                ++visited;
-                int c2 = nch, x2 = xr, v2 = visited;
-                if (lane == 0) c2 = ws_claim_blocking(ctr, cg, x2, v2, nch);
-                chunk = __builtin_amdgcn_readfirstlane(c2);
-                xr = __builtin_amdgcn_readfirstlane(x2);
-                visited = __builtin_amdgcn_readfirstlane(v2);
-              }
-            }
-          }
-          if (lane == 0) qring[(lc + 3) & (QN - 1)] = chunk;
-        }
-      });
-    }
-  }
-  // every claim of this workgroup has landed; the last workgroup out resets the counter block
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (tid == 0) {
-    const int d = __hip_atomic_fetch_add(ctr + SLOT_INTS - 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (d == (int)gridDim.x - 1) {
-      for (int x = 0; x < 8; ++x)
-        for (int c = 0; c < ncg; ++c) __hip_atomic_store(ctr + x * 8 + c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(ctr + SLOT_INTS - 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The attention projection with its residual add AND the LayerNorm that follows it (round 6,
-// es_gemm_nt_resid_ln): x = o W^T + b + x_in (fp32), h = LN(x) (bf16), mean / rstd -- for D = 384
+// The attention projection with its residual add AND the LayerNorm that follows it
+// (es_gemm_nt_resid_ln): x = o W^T + b + x_in (fp32), h = LN(x) (bf16), mean / rstd -- for D = 384
 // (ViT-S: N = K = 384).  Replaces es_gemm_nt(EPI_F32_RESID) + es_layernorm_fwd (code/models/conformer.py:
 // 65-66: x = x + attn(norm1(x)); norm2(x)) in one pass: x is never re-read from memory for its
-// statistics.  The weight-stationary body of gemm_nt_ws_kernel (W in registers, one persistent 8-wave
-// workgroup per CU, 32-row tiles) with whole rows per workgroup (one column group), so the row
-// statistics need no cross-workgroup exchange:
-//   ring (2 stages): the A tile (24 KiB, swizzled as in gemm_nt_ws_kernel) and the residual tile (32 rows x
-//     1,536 B, 16-B chunk c of row r at chunk c ^ (r & 15): conflict-free both for the MFMA-layout reads of
-//     the epilogue and for the LayerNorm's row reads), both by LDS-DMA one tile ahead;
+// statistics.  One persistent 8-wave workgroup per CU walks 32-row tiles of A and owns whole output rows, so
+// the row statistics need no cross-workgroup exchange:
+//   weights in registers: wave w keeps W[48 w .. 48 w + 48)[0 .. 384) for the whole launch as the MFMA A
+//     operand, 3 column fragments x 12 K fragments of v_mfma_f32_16x16x32_bf16 = 144 VGPRs, so the only
+//     operand stream is the A tile: staged into LDS once and consumed by all eight waves;
+//   ring (2 stages): the A tile (32 rows x 768 B = 24 KiB) and the residual tile (32 rows x 1,536 B), both
+//     with the 16-B chunk c of row r at chunk c ^ (r & 15) (swizzled on the DMA's source address; conflict-free
+//     for the MFMA fragment reads, for the MFMA-layout reads of the epilogue and for the LayerNorm's row
+//     reads), both by LDS-DMA one tile ahead;
+//   fragment address: the activation fragment of K step kk (0..11) for lane (g, r) is chunk 4 kk + g of row r,
+//     stored at chunk (4 kk + g) ^ r = 16 (kk >> 2) + 4 ((kk & 3) ^ (r >> 2)) + (g ^ (r & 3)): four per-lane
+//     bases (one per kk & 3) plus the constants 256 (kk >> 2) and 16 rows x 768 B for the second row block
+//     (rl_frag_addr);
+//   tiles are claimed from a per-stream counter (g_tile_ctr), two steps ahead of use.  The claim is inline asm
+//     (rl_claim_asm) retired by a COUNTED vmcnt at the end of the step: left to hipcc, the returning atomic
+//     is waited for where it is issued (vmcnt(0)), which also drains the next tile's LDS-DMA and the stores;
 //   per step: [vmcnt: tile i landed] [barrier] [DMA tile i + 1] [claim tile i + 2] [MFMAs] [x = acc + bias +
 //     residual, written over the residual tile in place] [barrier] [LayerNorm: one wave per row, 4 rows per
 //     wave, ln_fwd_kernel's lane map, warp sums and rounding as compiled (see the statistics below), so h /
@@ -1573,9 +1155,92 @@ constexpr int STAGE = TA + TX, NST = 2;
 constexpr int PA = TA / 1024 / 8, PX = TX / 1024 / 8;  // LDS-DMA instructions per wave per stage (3 + 6)
 constexpr int QN = 4;
 constexpr int LDS = NST * STAGE + QN * 4 + 16 + D * 4 * 3;  // ring, claim ring, scratch, bias, gamma, beta
-constexpr int SLOTS = 64, SLOT_INTS = 4;                    // per stream: [0] head, [3] done
 }  // namespace rlg
-__device__ int g_rl_ctr[rlg::SLOTS * rlg::SLOT_INTS];
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+// Tile counters of the persistent kernels (gemm_resid_ln_kernel, gemm_nt_ln_kernel): one block of 4 ints per HIP
+// stream (tile_ctr_slot), [0] the head the workgroups claim tiles from, [3] the count of workgroups done.
+// Launches on one stream do not overlap, so one block per stream serves both kernels.
+constexpr int CTR_SLOTS = 64, CTR_INTS = 4;
+__device__ int g_tile_ctr[CTR_SLOTS * CTR_INTS];
+// The end of a persistent kernel: every claim of this workgroup has landed; the last workgroup out resets the
+// block for the stream's next launch (no host-side reset: capturable).  A macro like the ISSUE blocks above, not a
+// force-inlined function: a function form changes gemm_nt_ln_kernel's SGPR allocation in its K loop, and this
+// file's kernels are held to the ISA they were measured with.
+#define TILE_CTR_RELEASE(CTR, TID)                                                                              \
+  {                                                                                                             \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                            \
+    if ((TID) == 0) {                                                                                           \
+      const int d_ = __hip_atomic_fetch_add((CTR) + CTR_INTS - 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+      if (d_ == (int)gridDim.x - 1) {                                                                           \
+        __hip_atomic_store((CTR), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                               \
+        __hip_atomic_store((CTR) + CTR_INTS - 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                \
+      }                                                                                                         \
+    }                                                                                                           \
+  }
+
+// A tile claim: one lane's returning agent-scope add (the same instruction hipcc emits for
+// __hip_atomic_fetch_add(.., __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)), as inline asm so that hipcc neither
+// waits for it nor moves the result to an SGPR right away; the caller retires it with a counted vmcnt and names
+// the destination again ("+v") before it reads the result (cdna_hip_programming.md §5.7 item 1, form ii;
+// audited in the .s: no copy of it between the two).
+__device__ __forceinline__ void rl_claim_asm(int* head, int& ret) {
+  unsigned long long save;
+  asm volatile(
+      "s_mov_b64 %1, exec\n\t"
+      "s_mov_b64 exec, 1\n\t"
+      "s_nop 4\n\t"
+      "global_atomic_add %0, %2, %3, off sc0\n\t"
+      "s_mov_b64 exec, %1"
+      : "=&v"(ret), "=&s"(save)
+      : "v"(head), "v"(1)
+      : "memory");
+}
+
+// The MFMA phase of a step: 24 activation fragments (2 row blocks x 12 K steps), each feeding 3 MFMAs, read by
+// inline-asm ds_read_b128 kept RL_PF ahead (hipcc, at ~240 VGPRs, issued each read right before its MFMAs and
+// waited for it: one LDS round trip per 3 MFMAs).  Each wait names its fragment ("+v", cdna_hip_programming.md
+// §5.7 item 1 form ii) so no MFMA is scheduled above it; LDS returns in order, so lgkmcnt(reads issued after
+// fragment t) retires fragment t.  xb4[kk & 3] are the four per-lane bases of the fragment address formula in
+// the kernel's header comment.
+constexpr int RL_PF = 4;
+__device__ __forceinline__ void rl_ds_read(bf16x8& x, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1" : "=v"(x) : "v"(addr) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void rl_lgkm_wait(bf16x8& x) {
+  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(x) : "i"(N) : "memory");
+}
+template <int T>
+__device__ __forceinline__ unsigned rl_frag_addr(const unsigned (&xb4)[4]) {
+  constexpr int kk = T % 12;
+  return xb4[kk & 3] + (T / 12) * 16 * rlg::ROWA + (kk >> 2) * 256;
+}
+template <int A, int T>
+__device__ __forceinline__ void rl_mfma_loop(f32x4 (&acc)[2][3], const bf16x8 (&wf)[3][12], const unsigned (&xb4)[4],
+                                             bf16x8 (&xs)[RL_PF]) {
+  if constexpr (T < 12) {
+    constexpr int after = (11 - T) < (RL_PF - 1) ? (11 - T) : (RL_PF - 1);
+    rl_lgkm_wait<after>(xs[T % RL_PF]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) acc[A][j] = mfma16(wf[j][T], xs[T % RL_PF], acc[A][j]);
+    if constexpr (T + RL_PF < 12) rl_ds_read(xs[T % RL_PF], rl_frag_addr<A * 12 + T + RL_PF>(xb4));
+    rl_mfma_loop<A, T + 1>(acc, wf, xb4, xs);
+  }
+}
+// row block A (16 rows) of a step: 12 fragments x 3 MFMAs
+template <int A>
+__device__ __forceinline__ void rl_mfma_half(f32x4 (&acc)[2][3], const bf16x8 (&wf)[3][12], const unsigned (&xb4)[4]) {
+  static_assert(RL_PF == 4, "prologue reads");
+#pragma unroll
+  for (int j = 0; j < 3; ++j) acc[A][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  bf16x8 xs[RL_PF];
+  rl_ds_read(xs[0], rl_frag_addr<A * 12 + 0>(xb4));
+  rl_ds_read(xs[1], rl_frag_addr<A * 12 + 1>(xb4));
+  rl_ds_read(xs[2], rl_frag_addr<A * 12 + 2>(xb4));
+  rl_ds_read(xs[3], rl_frag_addr<A * 12 + 3>(xb4));
+  rl_mfma_loop<A, 0>(acc, wf, xb4, xs);
+}
 
 // a a + b b with both products rounded (no contraction: __fmul_rn is a plain multiply in this HIP, so the
 // pragma is what keeps hipcc from fusing), and fma(a, a, b b)
@@ -1636,6 +1301,9 @@ __device__ __forceinline__ LnRow384 ln_row384(const float2 (&v)[3], bool even, f
   }
   return o;
 }
+// The stores of a finished row (x, h, mean, rstd: 8 VMEM stores, counted by the callers' vmcnt waits) stay written
+// out in both kernels: as one force-inlined helper hipcc compiled them differently (operand order in
+// gemm_resid_ln_kernel, 200 B of scratch in gemm_nt_ln_kernel).
 
 struct RLArgs {
   const float* gamma; const float* beta;
@@ -1653,7 +1321,7 @@ __global__ __launch_bounds__(512, 1) void gemm_resid_ln_kernel(NTArgs p, RLArgs 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, r = lane & 15;
-  int* const ctr = g_rl_ctr + slot * SLOT_INTS;
+  int* const ctr = g_tile_ctr + slot * CTR_INTS;
   const int nt = (p.M + R - 1) / R;
   if (tid == 0) {  // the first two tiles: blocking claims (their latency hides behind the weight loads)
     qring[0] = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1701,7 +1369,7 @@ __global__ __launch_bounds__(512, 1) void gemm_resid_ln_kernel(NTArgs p, RLArgs 
     for (int j = 0; j < PX; ++j)
       glds16_asm(x + (size_t)min(xr[j], lim) * p.ldaux * 4 + xc[j] * 16, S + TA + (j * 8 + w) * 1024);
   };
-  int xbase[4];  // the activation fragments' per-lane offsets (gemm_nt_ws_kernel's layout)
+  int xbase[4];  // the activation fragments' per-lane offsets within a stage (the four bases of rl_frag_addr)
 #pragma unroll
   for (int k = 0; k < 4; ++k) xbase[k] = r * ROWA + ((4 * (k ^ (r >> 2)) + (g ^ (r & 3))) << 4);
 
@@ -1743,7 +1411,7 @@ __global__ __launch_bounds__(512, 1) void gemm_resid_ln_kernel(NTArgs p, RLArgs 
       int claimed = nt, after_claim = 0;
       const bool claimer = w == 0;
       if (claimer) {
-        ws_claim_asm(ctr, claimed);
+        rl_claim_asm(ctr, claimed);
         seq += 1;
         after_claim = seq;
       }
@@ -1753,8 +1421,8 @@ __global__ __launch_bounds__(512, 1) void gemm_resid_ln_kernel(NTArgs p, RLArgs 
       for (int k = 0; k < 4; ++k)
         xb4[k] = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)(S + xbase[k]);
       f32x4 acc[2][3];
-      ws_mfma_half<0>(acc, wf, xb4);
-      ws_mfma_half<1>(acc, wf, xb4);
+      rl_mfma_half<0>(acc, wf, xb4);
+      rl_mfma_half<1>(acc, wf, xb4);
       // x = (acc + bias) + residual in the MFMA layout (lane: row 16 a + r, columns nw + 16 j + 4 g .. + 3),
       // written over the residual
       char* X = S + TA;
@@ -1806,14 +1474,7 @@ __global__ __launch_bounds__(512, 1) void gemm_resid_ln_kernel(NTArgs p, RLArgs 
       st ^= 1;
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (tid == 0) {
-    const int d = __hip_atomic_fetch_add(ctr + SLOT_INTS - 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (d == (int)gridDim.x - 1) {
-      __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(ctr + SLOT_INTS - 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  TILE_CTR_RELEASE(ctr, tid)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1824,7 +1485,7 @@ __global__ __launch_bounds__(512, 1) void gemm_resid_ln_kernel(NTArgs p, RLArgs 
 //   Main loop: the big-tile family's at 128 x 384 (gemm_nt_big_kernel's WM = 2, MF = 4, NF = 6: 8 waves of
 //     64 x 96), whole rows per workgroup, the same MFMA and ascending-K order as every NT kernel, so x carries
 //     es_gemm_nt(EPI_F32_RESID)'s bits.  Ring: BKT 64 x 2 stages (128 KiB) or BKT 32 x 3 stages (96 KiB).
-//   Tiles: one persistent workgroup per CU claims 128-row tiles from a per-stream counter (g_nl_ctr, reset by the
+//   Tiles: one persistent workgroup per CU claims 128-row tiles from a per-stream counter (g_tile_ctr, reset by the
 //     last workgroup out: capturable); the next claim is issued after the K loop and read after the epilogue.
 //   Epilogue: the ring is free once every wave has left the K loop; the tile goes through it in two 64-row slabs
 //     (slab s: each wave's row blocks 2 s, 2 s + 1; 96 KiB, gemm_resid_ln_kernel's chunk ^ (row & 15) layout):
@@ -1836,13 +1497,11 @@ namespace nlg {
 constexpr int TBM = 128, D = 384, WN = 4, MF = 4, NF = 6;
 constexpr int SLABR = 64, ROWX = D * 4, SLAB = SLABR * ROWX;  // 96 KiB
 constexpr int RPS = SLABR / 8;                                // LayerNorm rows per wave and slab
-constexpr int SLOTS = 64, SLOT_INTS = 4;                      // per stream: [0] head, [3] done
 template <int NST, int BKT>
 constexpr int body() { return NST * (TBM + D) * BKT * 2 > SLAB ? NST * (TBM + D) * BKT * 2 : SLAB; }
 template <int NST, int BKT>
 constexpr int lds() { return body<NST, BKT>() + 16 + D * 4 * 3; }  // ring / slab, the claim, bias, gamma, beta
 }  // namespace nlg
-__device__ int g_nl_ctr[nlg::SLOTS * nlg::SLOT_INTS];
 
 template <int NST, int BKT>
 __global__ __launch_bounds__(512, 1) void gemm_nt_ln_kernel(NTArgs p, RLArgs l, int slot) {
@@ -1860,7 +1519,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_ln_kernel(NTArgs p, RLArgs l, 
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w / WN, wn = w % WN;
   const int g = lane >> 4, r = lane & 15;
-  int* const ctr = g_nl_ctr + slot * SLOT_INTS;
+  int* const ctr = g_tile_ctr + slot * CTR_INTS;
   const int nt = (p.M + TBM - 1) / TBM;
   if (tid == 0) qslot[0] = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (tid < D / 4) {
@@ -2022,15 +1681,9 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_ln_kernel(NTArgs p, RLArgs l, 
     __builtin_amdgcn_s_barrier();  // slab 1 read, the next tile published
     cur = __builtin_amdgcn_readfirstlane(qslot[0]);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (tid == 0) {
-    const int d = __hip_atomic_fetch_add(ctr + SLOT_INTS - 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (d == (int)gridDim.x - 1) {
-      __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(ctr + SLOT_INTS - 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  TILE_CTR_RELEASE(ctr, tid)
 }
+#undef TILE_CTR_RELEASE
 
 // Launcher with every specialisation spelled out and launched by name (HIP_KERNEL_NAME keeps the
 // template commas out of the launch macro; a kernel referenced only through a function pointer
@@ -2094,7 +1747,7 @@ int launch_nt(int cfg, int epi, int grid, hipStream_t stream, const NTArgs& a) {
   }
 #define BIG_EPIS(WM_, MF_, NF_, NST_, BKT_) BIG_EPIS2(WM_, MF_, NF_, NST_, BKT_, 1)
 int launch_big(int cfg, int epi, int grid, hipStream_t stream, const NTArgs& a) {
-  if (cfg == 10 && epi == EPI_F32_RESID) BIG_LAUNCH(EPI_F32_RESID, 4, 4, 4, 3, 32, 4, 0, 0)  // plain stores
+  if (cfg == 10 && epi == EPI_F32_RESID) BIG_LAUNCH(EPI_F32_RESID, 4, 4, 4, 3, 32, 4, 0)  // plain stores
   switch (cfg) {
     case 10: BIG_EPIS2(4, 4, 4, 3, 32, 4)  // 256x128, BK32, 3 stages (72 KiB), two workgroups per CU
     default: BIG_EPIS(2, 8, 4, 2, 64)      // 6: 256x256, BK64, 2 stages (128 KiB)
@@ -2104,81 +1757,44 @@ int launch_big(int cfg, int epi, int grid, hipStream_t stream, const NTArgs& a) 
 #undef BIG_EPIS2
 #undef BIG_LAUNCH
 
-// The weight-stationary kernel's counter block for a stream: launches on one stream never overlap, so one block
-// per stream is never shared by two running launches (64 streams; beyond that streams share blocks by hash,
-// which is only wrong if two of them then run such GEMMs at the same time).
-static int ws_slot(hipStream_t s) {
-  static hipStream_t tab[wsg::SLOTS];
+// ---- the persistent kernels' launch plumbing (gemm_resid_ln_kernel, gemm_nt_ln_kernel) ----
+// The tile counter block of a stream (g_tile_ctr): launches on one stream never overlap, so one block per stream
+// is never shared by two running launches (64 streams; beyond that streams share blocks by hash, which is only
+// wrong if two of them then run such GEMMs at the same time).  The table is locked: trainers call the library
+// from more than one host thread.
+static int tile_ctr_slot(hipStream_t s) {
+  static std::mutex mu;
+  static hipStream_t tab[CTR_SLOTS];
   static int n = 0;
+  std::lock_guard<std::mutex> lock(mu);
   for (int i = 0; i < n; ++i)
     if (tab[i] == s) return i;
-  if (n < wsg::SLOTS) {
+  if (n < CTR_SLOTS) {
     tab[n] = s;
     return n++;
   }
-  return (int)(((uintptr_t)s >> 6) % wsg::SLOTS);
+  return (int)(((uintptr_t)s >> 6) % CTR_SLOTS);
 }
-static bool ws_fits(int epi, int N, int K) {
-  const bool e = epi == EPI_BF16 || epi == EPI_GELU || epi == EPI_GELU_ACT || epi == EPI_GELU_D || epi == EPI_F32;
-  return e && K == wsg::KD && N % wsg::NG == 0 && N / wsg::NG <= 8;
-}
-#define WS_LAUNCH(E, AUX_, ...)                                                                                   \
-  {                                                                                                                \
-    allow_lds(gemm_nt_ws_kernel<E, AUX_, ##__VA_ARGS__>, (size_t)wsg::LDS);                                       \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_nt_ws_kernel<E, AUX_, ##__VA_ARGS__>), dim3(grid), dim3(512), wsg::LDS, \
-                       stream, a, ncg, slot);                                                                      \
-    return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;                                                 \
-  }
-int launch_ws(int epi, hipStream_t stream, const NTArgs& a) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
+// one persistent workgroup per CU, at most one per tile
+static int persistent_grid(int tiles) {
+  static const int cus = [] {
+    int dev = 0, n = 0;
     (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
-  const int ncg = a.N / wsg::NG;
-  const int nrt = (a.M + wsg::R - 1) / wsg::R, nch = (nrt + wsg::CH - 1) / wsg::CH;
-  const int per = std::max(1, std::min(cus / ncg, nch));  // workgroups per column group
-  const int grid = per * ncg;
-  const int slot = ws_slot(stream);
-  static const int probe = getenv("ENDOSSL_WS_PROBE") ? atoi(getenv("ENDOSSL_WS_PROBE")) : 0;  // measurement only
-  if (probe == 5 && epi == EPI_BF16) WS_LAUNCH(EPI_BF16, 0, 5)
-  if (probe == 7 && epi == EPI_BF16) WS_LAUNCH(EPI_BF16, 0, 7)
-  switch (epi) {
-    case EPI_BF16: WS_LAUNCH(EPI_BF16, 0)
-    case EPI_GELU: WS_LAUNCH(EPI_GELU, 0)
-    case EPI_GELU_ACT: WS_LAUNCH(EPI_GELU_ACT, 0)
-    case EPI_GELU_D: WS_LAUNCH(EPI_GELU_D, 0)
-    case EPI_F32: WS_LAUNCH(EPI_F32, 0)
-    default: return ES_BAD_ARG;
-  }
+    return (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) ? 256 : n;
+  }();
+  return std::max(1, std::min(cus, tiles));
 }
-#undef WS_LAUNCH
 
 int launch_resid_ln(hipStream_t stream, const NTArgs& a, const RLArgs& l) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
-  const int nt = (a.M + rlg::R - 1) / rlg::R;
-  const int grid = std::max(1, std::min(cus, nt));
+  const int grid = persistent_grid((a.M + rlg::R - 1) / rlg::R);
   allow_lds(gemm_resid_ln_kernel, (size_t)rlg::LDS);
-  hipLaunchKernelGGL(gemm_resid_ln_kernel, dim3(grid), dim3(512), rlg::LDS, stream, a, l, ws_slot(stream));
+  hipLaunchKernelGGL(gemm_resid_ln_kernel, dim3(grid), dim3(512), rlg::LDS, stream, a, l, tile_ctr_slot(stream));
   return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
 }
 
 int launch_nt_ln(int ring, hipStream_t stream, const NTArgs& a, const RLArgs& l) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
-  const int nt = (a.M + nlg::TBM - 1) / nlg::TBM;
-  const int grid = std::max(1, std::min(cus, nt));
-  const int slot = ws_slot(stream);
+  const int grid = persistent_grid((a.M + nlg::TBM - 1) / nlg::TBM);
+  const int slot = tile_ctr_slot(stream);
   constexpr size_t lds3 = nlg::lds<3, 32>(), lds2 = nlg::lds<2, 64>();
   if (ring == 1) {  // BKT 32 x 3 stages
     allow_lds(gemm_nt_ln_kernel<3, 32>, lds3);
@@ -2198,14 +1814,7 @@ static int g_gemm_variant = -1;
 static int g_tn_variant = -1;
 static int g_small_tile = 1;  // the 64 x 128 tile rules (es_set_gemm_small_tile; 0 = without them)
 
-
 extern "C" {
-
-// measurement builds only (ENDOSSL_WS_PROBE=7): the weight-stationary kernel's step stamps (not part of the es_ ABI)
-int endossl_ws_debug_stamps(unsigned long long* host, int n) {
-  if (n > WS_DBG) n = WS_DBG;
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_ws_dbg), n * sizeof(unsigned long long)) == hipSuccess ? 0 : -3;
-}
 
 int es_gemm_tn_ex(const void* A1, int ld1, const void* A2, int ld2, int M, int N1, int N2, int splits,
                   float* workspace, float* out, int accumulate, float* bias_out, int variant, hipStream_t stream);
@@ -2241,11 +1850,6 @@ int es_gemm_nt(int epi, const void* A, int lda, const void* B, int ldb, const fl
   //    behind the 8 waves' K loop at one workgroup per CU (S1 fc2 dgrad 1.97 vs 1.65 ms on the ring).
   //  es_set_gemm_small_tile(0) drops the 64 x 128 rules.
   int variant = g_gemm_variant;
-  const bool two_wg = true;
-  if (variant == 12) {  // the weight-stationary kernel where it applies, the per-shape rules elsewhere
-    if (ws_fits(epi, N, K)) return launch_ws(epi, stream, a);
-    variant = -1;
-  }
   if (variant < 0) {
     const bool gelu = epi == EPI_GELU || epi == EPI_GELU_ACT || epi == EPI_GELU_D;
     const bool plain = epi == EPI_BF16 || epi == EPI_F32 || epi == EPI_F32_RESID || epi == EPI_MULAUX;
@@ -2253,9 +1857,9 @@ int es_gemm_nt(int epi, const void* A, int lda, const void* B, int ldb, const fl
       variant = 11;
     else if (g_small_tile && M < 32768 && epi == EPI_GELU_ACT)
       variant = 11;
-    else if (two_wg && M >= 65536 && K >= 768 && N == 384 && epi == EPI_BF16)
+    else if (M >= 65536 && K >= 768 && N == 384 && epi == EPI_BF16)
       variant = 0;
-    else if (two_wg && (plain || epi == EPI_GELU_D) && M >= 65536 && ((K <= 384 && N >= 384) || (K >= 768 && N == 384)))
+    else if ((plain || epi == EPI_GELU_D) && M >= 65536 && ((K <= 384 && N >= 384) || (K >= 768 && N == 384)))
       variant = 10;
     else if (K <= 384 && N % 256 == 0 && epi == EPI_MULAUX)
       variant = M < 65536 ? 0 : 6;
@@ -2353,9 +1957,10 @@ int endossl_nt_ln_ring(int v) {
 // 6 = 256x256 BK64 2-stage (8 waves of 128x64, one workgroup per CU, N % 256 == 0); 10 = 256x128 BK32
 // 3-stage, 64x64 per wave, two workgroups per CU (N % 128 == 0); 11 = 64x128 (waves of 32x64) BK64
 // 2-stage).  Returns the previous value, or ES_BAD_ARG (state unchanged) for a family that does not
-// exist (the others were measured slower and removed in round 4).
+// exist (the others were measured slower and removed: most in round 4, the weight-stationary K = 384
+// kernel, once 12, after round 6 -- DESIGN.md §5).
 static bool gemm_variant_ok(int v) {
-  return v == -1 || v == 0 || v == 1 || v == 2 || v == 5 || v == 6 || v == 10 || v == 11 || v == 12;
+  return v == -1 || v == 0 || v == 1 || v == 2 || v == 5 || v == 6 || v == 10 || v == 11;
 }
 int es_set_gemm_variant(int v) {
   if (!gemm_variant_ok(v)) return ES_BAD_ARG;
@@ -2453,14 +2058,14 @@ int es_gemm_tn_ex(const void* A1, int ld1, const void* A2, int ld2, int M, int N
     allow_lds(gemm_tn_kernel<BKM_, NST_>, lds);                                                       \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_tn_kernel<BKM_, NST_>), dim3(grid), dim3(256), lds, stream, a); \
   }
-#define TNB_LAUNCH(BKM_, NST_, ASM_, ...)                                                               \
+#define TNB_LAUNCH(BKM_, NST_)                                                                          \
   {                                                                                                   \
     const size_t lds = (size_t)NST_ * BKM_ * (TB1 + TB2) * 2;                                         \
-    allow_lds(gemm_tn_big_kernel<BKM_, NST_, ASM_, ##__VA_ARGS__>, lds);                              \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_tn_big_kernel<BKM_, NST_, ASM_, ##__VA_ARGS__>), dim3(grid), dim3(512), lds, stream, a); \
+    allow_lds(gemm_tn_big_kernel<BKM_, NST_>, lds);                                                   \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_tn_big_kernel<BKM_, NST_>), dim3(grid), dim3(512), lds, stream, a); \
   }
   switch (v) {
-    case 7: TNB_LAUNCH(64, 2, true) break;
+    case 7: TNB_LAUNCH(64, 2) break;
     default: TN_LAUNCH(32, 2) break;  // 0
   }
 #undef TN_LAUNCH

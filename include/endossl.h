@@ -59,9 +59,7 @@ int es_gemm_nt_resid_ln(const void* A, int lda, const void* B, int ldb, const fl
 int es_gemm_nt_ln(const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc,
                   const float* aux, int ldaux, const float* gamma, const float* beta, void* h, int ldh, float* mean,
                   float* rstd, int M, int N, int K, float eps, hipStream_t stream);
-/* tuning knob: NT kernel family (-1 = per-shape default; 0, 1, 2, 5, 6, 10, 11 = fixed tilings, see gemm.hip;
- * 12 = the weight-stationary K = 384 kernel where it applies -- epi 0 / 1 / 4 / 6 / 7, K == 384, N a multiple
- * of 384 up to 3072 -- and the per-shape rules elsewhere; opt-in, bit-identical to the tilings);
+/* tuning knob: NT kernel family (-1 = per-shape default; 0, 1, 2, 5, 6, 10, 11 = fixed tilings, see gemm.hip);
  * returns the old one, or -2 (state unchanged) for a family that does not exist */
 int es_set_gemm_variant(int variant);
 /* 1 (default): the 64 x 128 NT tile rules (N <= 384 outputs of small token shards, M < 32768, and the residual
