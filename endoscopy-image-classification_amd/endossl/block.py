@@ -80,15 +80,11 @@ nop = lambda *args: None  # noqa: E731 -- a callback the owner does not use
 
 
 class Rows:
-    """A row set: the block's buffers, by the chain's names, for images [i0, i0 + n) of T token rows each (T = 1:
-    compact CLS rows); with i0 > 0 each starts at its row i0 * T (lse / delta, per image, head and token: i0 * T * H).
-    ldx / lddxm: the row strides of x and d(xmid) where they are the CLS rows of a full token buffer."""
+    """A row set: the block's buffers, by the chain's names, for n images of T token rows each (T = 1: compact CLS
+    rows).  ldx / lddxm: the row strides of x and d(xmid) where they are the CLS rows of a full token buffer."""
 
-    def __init__(self, n, T, H, i0=0, ldx=None, lddxm=None, **bufs):
+    def __init__(self, n, T, H, ldx=None, lddxm=None, **bufs):
         self.n, self.T, self.rows, self.ldx, self.lddxm = n, T, n * T, ldx, lddxm
-        if i0:
-            r0 = i0 * T
-            bufs = {k: t[r0 * H:] if k in ("lse", "delta") else t[r0:] for k, t in bufs.items()}
         self.__dict__.update(bufs)
 
 

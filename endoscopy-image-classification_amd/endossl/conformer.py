@@ -271,16 +271,6 @@ class _Map:
 CONF_TN_SHARE = 0.5
 
 
-# a transformer block's four weight gradients (fc2, fc1, proj, qkv) as ONE es_gemm_tn_big_grouped launch (384 x 192
-# tiles, split-K over the tokens) plus one reduce, issued on the side stream once the block's last data gradient
-# is made -- instead of four es_gemm_tn launches on the 128 x 128 tile (Conformer-B / 384: 938 us of weight
-# gradients per block alone on the chip); sized to CONF_TN_SHARE of the CUs beside the branch streams.  Off: S1
-# wall neutral (126.5 vs 126.6 ms, the side stream already hid the per-Linear launches), and at one split per tile
-# (96 tiles on a 128-workgroup share) its fp32 chains over 36,928 tokens put the proj / qkv weight gradients at
-# 1.05-1.16e-5 of the exact product of the device's own inputs, above tests/test_gpu_s1_blocks.py's 1e-5 bar
-CONF_TN_GROUPED = False
-
-
 def _chain(m):
     """The transformer blocks' launch chain over the model's parameters and weight images (the engine's defaults)."""
     return block.Chain(call, m.pview, m.gview, m.wb, m.wt, m.cfg.heads, LN_EPS)
@@ -904,15 +894,7 @@ class _BlockFn(torch.autograd.Function):
         block.cast_f32_bf16(call, dout, R.dxb, Mp * D)
         ws_ln = torch.empty(2 * 1024 * D, device=dev)
 
-        # the grouped launch's shapes: every N1 a multiple of 384, every N2 of 192; rows [M, Mp) of every
-        # operand zero (h1 / o / h2 / act zero-padded in the forward, the dy scratch zeroed once), Mp >= M + 63
-        grouped = (CONF_TN_GROUPED and xt.is_cuda and D % 384 == 0 and Hd % 384 == 0 and Mp >= _rup(M, 64))
-        probs = []
-
         def wgrad(dy, N1, x, N2, Mw, out, bias_out, label=None):
-            if grouped:
-                probs.append((dy, N1, x, N2, Mw, out, bias_out, N1, N2))
-                return
             sp = 0  # es_gemm_tn sizes the split-K for the kernel it picks
             if side is not None and CONF_TN_SHARE < 1.0 and M >= 65536 and N1 % 384 == 0 and N2 % 192 == 0:
                 # beside the branch streams: the 384 x 192 tile on a share of the CUs (as Engine.TN_SHARE)
@@ -926,12 +908,6 @@ class _BlockFn(torch.autograd.Function):
             block.layernorm_bwd(call, dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, ws_ln, 1024, Ml, D, 0)
 
         def before_ln1():
-            if probs:  # the block's four weight gradients as one grouped launch (CONF_TN_GROUPED)
-                ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-                target = max(1, int(ncu * CONF_TN_SHARE)) if side is not None else ncu
-                with block.on_stream(side, main):
-                    block.tn_big_grouped(probs, target, lambda need: m.bwd_scratch(
-                        f"tn_grouped_ws/{k}", (max(int(need), 1),), torch.float32))
             R.dx = _zero_pad(torch.empty(Mp, D, device=dev), M)  # returned to autograd: fresh
 
         ch = _chain(m)

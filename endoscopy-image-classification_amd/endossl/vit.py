@@ -18,6 +18,7 @@ MI355X-first layout:
     `model(x)` / `loss.backward()` still work as a drop-in nn.Module.
 """
 import ctypes
+import functools
 import math
 import os
 
@@ -161,8 +162,9 @@ class _Acts:
         D, Hd, L = cfg.dim, cfg.hidden, cfg.depth
         self.n, self.train = n, train
         self.M = n * cfg.T
-        # 256 rows beyond the padded token count: a half-batch lane's GEMM tiles (Engine.SHARD_LANES) start at
-        # an image boundary and read up to 256 rows past their last token
+        # 256 rows beyond the padded token count.  They were added for the removed two-lane backward; whether the
+        # strided CLS-row weight gradients (ld1 = T * 3D over n rows) can read past _rup(M, 256) without them has
+        # not been established, so the size stays
         Mp = _rup(self.M, 256) + 256
         self.Mp = Mp
         Lk = L if train else 1
@@ -199,7 +201,7 @@ class _Grads:
 
     def __init__(self, cfg, n, device, b16=torch.bfloat16):
         D, Hd = cfg.dim, cfg.hidden
-        Mp = _rup(n * cfg.T, 256) + 256  # (+ 256: the half-batch lanes' tile over-read, as _Acts)
+        Mp = _rup(n * cfg.T, 256) + 256  # (+ 256: as _Acts, kept until the strided reads' reach is established)
         f32 = torch.float32
         z = lambda *s, dt=f32: torch.zeros(*s, dtype=dt, device=device)  # noqa: E731
         self.n = n
@@ -219,6 +221,93 @@ class _Grads:
         self.c_dpre, self.c_dxmb, self.c_do = z(Mc, Hd, dt=b16), z(Mc, D, dt=b16), z(Mc, D, dt=b16)
         self.c_dh = z(Mc, D, dt=b16) if Engine.DH_BF16 else z(Mc, D)
         self.dxm_cls = z(Mp, D)
+
+
+class _WgradSchedule:
+    """The ordering decisions of one reverse pass (Engine.backward): where each weight-gradient GEMM runs, which dY
+    set a layer uses, when the side stream's events are recorded and waited on.  No C-ABI calls, no tensor maths:
+    the launches are the owner's callables, run under on_stream(side, main) where they go beside the chain.
+
+    mode "each":    one launch per GEMM (wgrad), on the side stream when there is one, else on the caller's;
+         "layer":   Engine.LAYER_WGRAD -- a block's GEMMs on the 384 x 192 tile over at least min_m rows as one
+                    wgrad_layer(problems, i) launch once its last dY is made (before_ln1), the rest as "each";
+         "grouped": Engine.GROUP_WGRAD -- every GEMM recorded, one launch_grouped(problems, slot) per group_layers
+                    blocks beside the chain and one (slot 0) after it on the caller's stream.
+    defer: the list the LayerNorm backwards leave their parameter-gradient partials in (Engine.DEFER_LN_GRADS),
+    reduced by ln_flush(defer) with the weight-gradient launches; None: reduced on the chain."""
+
+    def __init__(self, sets, M, depth, grouped, *, layer_wgrad, defer_ln, bf16, capture, group_layers, min_m, main,
+                 side, wgrad, wgrad_layer, launch_grouped, ln_flush, grad_ready=None, block_range=None,
+                 on_stream=block.on_stream):
+        self.mode = "grouped" if grouped else "layer" if layer_wgrad and bf16 and M >= min_m else "each"
+        self.defer = [] if defer_ln and grad_ready is None and not capture and self.mode != "each" else None
+        self.sets, self.depth, self.group_layers, self.min_m = sets, depth, group_layers, min_m
+        self.main, self.side, self.on_stream = main, side, on_stream
+        self._wgrad, self._wgrad_layer, self._launch_grouped, self._ln_flush = wgrad, wgrad_layer, launch_grouped, ln_flush
+        self.grad_ready, self.block_range = grad_ready, block_range
+        self.problems = []  # recorded GEMMs ("layer": this block's; "grouped": since the last grouped launch)
+        self.done = {}  # block -> the side-stream event after its weight gradients (overlapped, not grouped)
+
+    def grad_sets(self, i):
+        """(Gi, Gn): the sets of block i's dY images and of the next block's (i - 1) bf16 d(block output).  Two
+        alternating sets, or ("grouped") one per layer and the spare for the embedding's."""
+        if self.mode == "grouped":
+            return self.sets[i], self.sets[i - 1] if i > 0 else self.sets[self.depth]
+        return self.sets[i % 2], self.sets[(i - 1) % 2]
+
+    def wgrad(self, dy, N1, x, N2, M, out, bias_out=None, ld1=None, ld2=None, label=None):
+        """The chain's callback once dy is made: out = dy^T x launched beside the chain, or recorded for the
+        block's / the group's one launch."""
+        l1, l2 = ld1 or N1, ld2 or N2
+        if self.mode == "grouped" or (self.mode == "layer" and M >= self.min_m and N1 % 384 == 0 and N2 % 192 == 0
+                                      and l1 % 8 == 0 and l2 % 8 == 0):
+            self.problems.append((dy, N1, x, N2, M, out, bias_out, l1, l2, label))
+            return
+        with self.on_stream(self.side, self.main):
+            self._wgrad(dy, N1, x, N2, M, out, bias_out, ld1=ld1, ld2=ld2, label=label)
+
+    def _flush_layer(self, i):
+        """"layer": block i's recorded GEMMs as one launch (and the LayerNorm gradients deferred so far)."""
+        if self.mode != "layer" or not (self.problems or self.defer):
+            return
+        with self.on_stream(self.side, self.main):
+            if self.problems:
+                self._wgrad_layer(self.problems, i)
+                self.problems.clear()
+            if self.defer:
+                self._ln_flush(self.defer)
+
+    def before_ln1(self, i):
+        """Block i's weight gradients are all recorded; its LayerNorm 1 backward is about to write the other set."""
+        self._flush_layer(i)
+        if self.side is not None and self.mode != "grouped":
+            self.done[i] = self.side.record_event()
+            if i + 1 in self.done:  # set (i - 1) % 2 was layer i + 1's: its weight gradients must be done
+                self.main.wait_event(self.done.pop(i + 1))
+
+    def block_done(self, i):
+        """After block i's chain: the group's launch beside the rest of the chain (its dY sets are never rewritten
+        within the step), then grad_ready(lo, hi, events) for the block's parameters."""
+        if self.mode == "grouped" and i > 0 and i % self.group_layers == 0 and self.problems:
+            with self.on_stream(self.side, self.main):
+                self._launch_grouped(self.problems, i)
+                if self.defer:
+                    self._ln_flush(self.defer)
+            self.problems.clear()
+        if self.grad_ready is not None:
+            evs = [self.main.record_event()] + ([self.done[i]] if i in self.done else [])
+            self.grad_ready(*self.block_range(i), evs)
+
+    def finish(self):
+        """After the embedding backward and the patch weight gradient: what is still recorded or deferred, then
+        the caller's stream joins the side stream."""
+        self._flush_layer(-1)
+        if self.mode == "grouped":
+            self._launch_grouped(self.problems, 0)
+        if self.defer:
+            self._ln_flush(self.defer)
+        if self.side is not None:
+            self.main.wait_stream(self.side)
 
 
 class Engine:
@@ -244,12 +333,6 @@ class Engine:
     GROUP_WGRAD = "auto"
     GROUP_WGRAD_MAX_M = 16384
     GROUP_LAYERS = 6
-    # ... and the data-gradient chain of blocks depth-2..0 as TWO lanes, the train images' halves on the caller's
-    # stream and the side stream, the grouped weight gradients on a third stream after both lanes.  The second
-    # stream is worth 13 % at N = 8 (6.25 -> 5.41 ms, weak forward / weight gradients beside the chain), but the
-    # split chain measured slower: 5.35 / 5.35 / 5.44 vs 5.30 / 5.29 / 5.29 ms (r05, one box, interleaved; the
-    # half-batch kernels lose more than the concurrency gains).  Off; bit-identical when on (test_gpu_step.py).
-    SHARD_LANES = False
     # the LayerNorm backwards' parameter-gradient reductions off the data-gradient chain: each backward leaves its
     # per-workgroup partials in a workspace of its own and one es_ln_param_grads_multi launch per weight-gradient
     # launch reduces them on the side stream (24 launches fewer on the chain per step; bit-identical)
@@ -328,8 +411,8 @@ class Engine:
         self._ws_lnp = None
         self._lnp_next = 0
         self._side = None
-        self._ncu = None
-        self._lane_state, self._gtab = {}, {}
+        self._ncu_cache = None
+        self._gtab = {}
         self._grad_b = None
         self.overlap = self.OVERLAP
         self.overlap_fwd = self.OVERLAP_FWD
@@ -408,26 +491,28 @@ class Engine:
             self._acts[key] = _Acts(self.cfg, n, train, self.device, self.op_dtype)
         return self._acts[key]
 
-    def workspace(self, lane=0):
-        """Split-K slabs of the weight-gradient GEMMs (one per backward lane: lanes run concurrently)."""
+    def workspace(self):
+        """Split-K slabs of the weight-gradient GEMMs."""
         if self._ws is None:
-            self._ws = {}
-        if lane not in self._ws:
             cfg = self.cfg
             D, Hd = cfg.dim, cfg.hidden
             n_tn = max(a * b for a, b in ((3 * D, D), (D, D), (Hd, D), (D, Hd), (D, 3 * cfg.patch * cfg.patch)))
-            self._ws[lane] = torch.empty(self.TN_MAX_SPLITS * n_tn + 2 * 1024 * max(Hd, 3 * D), dtype=torch.float32,
-                                         device=self.device)
-        return self._ws[lane]
+            self._ws = torch.empty(self.TN_MAX_SPLITS * n_tn + 2 * 1024 * max(Hd, 3 * D), dtype=torch.float32,
+                                   device=self.device)
+        return self._ws
 
-    def ln_workspace(self, lane=0):
+    def ln_workspace(self):
         """LayerNorm-backward partials (separate from the split-K slabs: the two run on different
         streams when the weight gradients overlap the data-gradient chain)."""
         if self._ws_ln is None:
-            self._ws_ln = {}
-        if lane not in self._ws_ln:
-            self._ws_ln[lane] = torch.empty(2 * LN_BWD_BLOCKS * self.cfg.dim, dtype=torch.float32, device=self.device)
-        return self._ws_ln[lane]
+            self._ws_ln = torch.empty(2 * LN_BWD_BLOCKS * self.cfg.dim, dtype=torch.float32, device=self.device)
+        return self._ws_ln
+
+    def _ncu(self):
+        """The device's CU count (the CU-share sizing of the weight-gradient launches)."""
+        if self._ncu_cache is None:
+            self._ncu_cache = torch.cuda.get_device_properties(self.device).multi_processor_count
+        return self._ncu_cache
 
     def side_stream(self, tokens=0):
         """The second HIP stream (weak forward beside the train forward; weight gradients beside
@@ -439,12 +524,6 @@ class Engine:
         if prio not in self._side:
             self._side[prio] = torch.cuda.Stream(device=self.device, priority=prio)
         return self._side[prio]
-
-    def third_stream(self):
-        """A third HIP stream: the small shard's grouped weight gradients beside the two chain lanes."""
-        if getattr(self, "_third", None) is None:
-            self._third = torch.cuda.Stream(device=self.device)
-        return self._third
 
     # -------------------------------------------------------------- forward
     def forward(self, flat, images_list, train):
@@ -521,8 +600,7 @@ class Engine:
         return A.logits
 
     def _prune(self):
-        """PRUNE_LAST in effect (read at each forward / backward: tests override it per instance);
-        the two-lane backward runs every row."""
+        """PRUNE_LAST in effect (read at each forward / backward: tests override it per instance)."""
         return self.PRUNE_LAST
 
     def _cls_rows(self, A, n, xin=None, G=None):
@@ -543,10 +621,8 @@ class Engine:
         weight gradients overlapped on the side stream and TN_SHARE < 1, the 384 x 192 tile's launches
         are sized to that share of the CUs (the rest stay free for the data-gradient chain)."""
         if self._tn_shared(M, N1, N2):
-            if self._ncu is None:
-                self._ncu = torch.cuda.get_device_properties(self.device).multi_processor_count
             tiles = (N1 // 384) * (N2 // 192)
-            return max(1, int(self._ncu * self.TN_SHARE) // tiles)
+            return max(1, int(self._ncu() * self.TN_SHARE) // tiles)
         return 0
 
     def _tn_shared(self, M, N1, N2):
@@ -557,10 +633,10 @@ class Engine:
         return (self.TN_SHARE < 1.0 and self.overlap and M >= self.TN_SHARE_MIN_M and N1 % 384 == 0
                 and N2 % 192 == 0 and self.precision == "bf16")
 
-    def _wgrad(self, dy, N1, x, N2, M, out, bias_out=None, lane=0, ld1=None, ld2=None, label=None):
+    def _wgrad(self, dy, N1, x, N2, M, out, bias_out=None, ld1=None, ld2=None, label=None):
         """out = dy^T x (weight grad) and, fused, bias_out = column sums of dy (row strides ld1 / ld2,
         default N1 / N2).  `label`: a launch site the bench can time with HIP events (self.probe)."""
-        ws = self.workspace(lane)
+        ws = self.workspace()
         splits = self._tn_splits(M, N1, N2)
         need = getattr(_lib.load(), "es_gemm_tn_f32_workspace" if self.precision == "fp32" else "es_gemm_tn_workspace")
         if need(N1, N2, splits) > ws.numel():
@@ -575,8 +651,7 @@ class Engine:
             fn, args = "es_gemm_tn_ex", args + (variant, _lib.stream())
         self._bracket(label, 2.0 * M * N1 * N2, lambda: self._call(fn, *args))
 
-    def _ln_bwd(self, dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, M, lane=0, lddx=None, accumulate=0,
-                defer=None):
+    def _ln_bwd(self, dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, M, lddx=None, defer=None):
         """defer (a list): the parameter gradients' partials stay in a workspace of their own, recorded in
         `defer` for one es_ln_param_grads_multi launch later (Engine.DEFER_LN_GRADS)."""
         D = self.cfg.dim
@@ -586,10 +661,10 @@ class Engine:
             self._lnp_next += 1                           # may reduce a flushed one after the chain moved on)
             block.layernorm_bwd(self._call, dy, x, mean, rstd, gamma, dres, dx, dxb, None, None, ws, LN_BWD_BLOCKS, M,
                                 D, 0, lddx)
-            defer.append((ws, dgamma, dbeta, grid, accumulate))
+            defer.append((ws, dgamma, dbeta, grid, 0))  # (the entry's `acc` field: overwrite)
             return
-        block.layernorm_bwd(self._call, dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, self.ln_workspace(lane),
-                            LN_BWD_BLOCKS, M, D, accumulate, lddx)
+        block.layernorm_bwd(self._call, dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, self.ln_workspace(),
+                            LN_BWD_BLOCKS, M, D, 0, lddx)
 
     def ln_part_workspace(self, k):
         """The k-th deferred LayerNorm backward's partials of a reverse pass (Engine.DEFER_LN_GRADS)."""
@@ -633,85 +708,21 @@ class Engine:
             raise ValueError("Engine.backward needs dlogits (cls head) or dfts (emb head)")
         n = int(top.shape[0])
         A = self.acts(n, True)
-        if n not in self._grads:
-            # two sets: layer i's weight-gradient inputs (dY images) live in set i % 2, so the side
-            # stream can still read layer i+1's while the main stream writes layer i's
-            self._grads[n] = (_Grads(cfg, n, self.device, self.op_dtype), _Grads(cfg, n, self.device, self.op_dtype))
-        G = self._grads[n][0]
-        GS = self._grads[n]
-        D, Hd, T, M = cfg.dim, cfg.hidden, cfg.T, A.M
+        D, T, M = cfg.dim, cfg.T, A.M
         gv = lambda name: self.view(grad, name)  # noqa: E731
         fv = lambda name: self.view(flat, name)  # noqa: E731
-        ov = self.overlap
-        main = torch.cuda.current_stream(self.device)
-        side = self.side_stream(M) if ov else None
         grouped = self._grouped_wgrad(M, grad_ready)
-        if grouped:
-            # one dY set per layer (+ a spare for layer 0's unused dY of the embedding): the grouped launch
-            # at the end reads every layer's weight-gradient inputs
-            key = (n, "grouped")
-            if key not in self._grads:
-                self._grads[key] = [G] + [_Grads(cfg, n, self.device, self.op_dtype) for _ in range(cfg.depth)]
-            GS = self._grads[key]
-        ovw = ov and not grouped
-        nh = n // 2
-        lanes = (grouped and ov and self.SHARD_LANES and self.capture is None and n % 2 == 0 and nh > 0
-                 and self.precision == "bf16")
-        third = self.third_stream() if lanes else None
-        problems = []
-        layer_wg = self.LAYER_WGRAD and not grouped and self.precision == "bf16" and M >= self.TN_SHARE_MIN_M
-        lp = []  # this block's long-axis weight gradients (layer_wg): one grouped launch at the block's end
-        # deferred LayerNorm parameter gradients (Engine.DEFER_LN_GRADS): reduced with the weight-gradient launches
-        lnd = ([] if self.DEFER_LN_GRADS and grad_ready is None and self.capture is None and not lanes
-               and (grouped or layer_wg) else None)
+        GS = self._grad_sets(n, grouped)
+        G = GS[0]  # everything but a layer's dY images
+        sched = _WgradSchedule(
+            GS, M, cfg.depth, grouped, layer_wgrad=self.LAYER_WGRAD, defer_ln=self.DEFER_LN_GRADS,
+            bf16=self.precision == "bf16", capture=self.capture is not None, group_layers=self.GROUP_LAYERS,
+            min_m=self.TN_SHARE_MIN_M, main=torch.cuda.current_stream(self.device),
+            side=self.side_stream(M) if self.overlap else None, wgrad=self._wgrad, wgrad_layer=self._wgrad_layer,
+            launch_grouped=self._launch_grouped, ln_flush=self._ln_grads_flush, grad_ready=grad_ready,
+            block_range=self._block_range)
         self._lnp_next = 0
-
-        def wgrad_side(dy, N1, x, N2, Mw, out, bias_out=None, ld1=None, ld2=None, label=None):
-            """Weight-gradient GEMM on the side stream once the main stream has produced dY (or, grouped,
-            recorded for the one launch after the chain / at the end of the block)."""
-            if grouped:
-                problems.append((dy, N1, x, N2, Mw, out, bias_out, ld1 or N1, ld2 or N2))
-                return
-            if (layer_wg and Mw >= self.TN_SHARE_MIN_M and N1 % 384 == 0 and N2 % 192 == 0
-                    and (ld1 or N1) % 8 == 0 and (ld2 or N2) % 8 == 0):
-                lp.append((dy, N1, x, N2, Mw, out, bias_out, ld1 or N1, ld2 or N2, label))
-                return
-            with block.on_stream(side, main):
-                self._wgrad(dy, N1, x, N2, Mw, out, bias_out, ld1=ld1, ld2=ld2, label=label)
-
-        done = {}
-
-        def flush_layer(i):
-            """Block i's recorded weight gradients as one grouped split-K launch on the side stream (and the
-            LayerNorm parameter gradients deferred so far)."""
-            if not lp and not (layer_wg and lnd):
-                return
-            with block.on_stream(side, main):
-                if lp:
-                    self._wgrad_layer(lp, i)
-                    lp.clear()
-                if layer_wg and lnd:
-                    self._ln_grads_flush(lnd)
-
-        def block_done(i):
-            if self.capture is not None:
-                self.capture("bwd", True, i, G.dx[:M])
-            if grouped and i > 0 and i % self.GROUP_LAYERS == 0 and problems:
-                # these layers' weight gradients as one grouped launch on the side stream (two lanes: a third
-                # stream after both), beside the rest of the data-gradient chain (their dY sets are never
-                # rewritten within the step)
-                with block.on_stream(third, main, side) if lanes else block.on_stream(side, main):
-                    self._launch_grouped(problems, i)
-                    if lnd:  # (None with lanes)
-                        self._ln_grads_flush(lnd)
-                problems.clear()
-            if grad_ready is None:
-                return
-            lo = self.offs[f"blocks.{i}.norm1.weight"]
-            hi = self.offs[f"blocks.{i + 1}.norm1.weight" if i + 1 < cfg.depth else "norm.weight"]
-            evs = [main.record_event()] + ([done[i]] if i in done else [])
-            grad_ready(lo, hi, evs)
-
+        ln_bwd = functools.partial(self._ln_bwd, defer=sched.defer)
         # zero_grad: no zero fill of the flat gradient -- every entry of it is written by its first writer of the
         # reverse pass (the head / final-norm kernel with accumulate = 0, the LayerNorm and weight-gradient
         # reductions and the embedding backward overwrite); test_gpu_step.py checks a NaN-filled buffer.  The
@@ -719,7 +730,7 @@ class Engine:
         if zero_grad and cfg.head == "emb":
             grad.zero_()
         prune = self._prune()
-        GL = GS[cfg.depth - 1] if grouped else GS[(cfg.depth - 1) % 2]
+        GL = sched.grad_sets(cfg.depth - 1)[0]  # the last block's dY set
         # d(loss)/d(CLS tokens after the last block): compact rows (prune) or the CLS rows of G.dx
         dtop, Tt = (GL.c_dx, 1) if prune else (G.dx, T)
         if not prune:
@@ -741,94 +752,66 @@ class Engine:
         else:
             block.cast_f32_bf16(self._call, G.dx, GL.dxb, M * D)
         ch = self._chain(flat, grad)
-        ln_bwd = lambda *a, **kw: self._ln_bwd(*a, defer=lnd, **kw)  # noqa: E731
         cap = block.nop  # test hook: each reverse-pass intermediate of a full-row block as the next op reads it
         for i in reversed(range(cfg.depth)):
             b = f"blocks.{i}."
-            if grouped:
-                Gi, Gn = GS[i], GS[i - 1] if i > 0 else GS[cfg.depth]
-            else:
-                Gi, Gn = GS[i % 2], GS[(i - 1) % 2]
+            Gi, Gn = sched.grad_sets(i)
+            before_ln1 = functools.partial(sched.before_ln1, i)
             if self.capture is not None:
-                cap = lambda kind, *ts, i=i: self.capture(kind, True, i, *(t[:M] for t in ts))  # noqa: E731
-
-            def before_ln1(i=i):
-                flush_layer(i)
-                if ovw:
-                    done[i] = side.record_event()
-                    if i + 1 in done:  # set (i-1) % 2 was layer i+1's: its weight gradients must be done
-                        main.wait_event(done.pop(i + 1))
-            if lanes and not (prune and i == cfg.depth - 1):
-                if i == (cfg.depth - 2 if prune else cfg.depth - 1):
-                    side.wait_stream(main)  # lane 1 starts from the last block's (or the head's) output gradient
-                self._lanes_block(ch, b, A, G, Gi, Gn, i, n, nh, main, side)
-                wgrad_side(Gi.dxb, D, A.act[i], Hd, M, gv(b + "mlp.fc2.weight"), gv(b + "mlp.fc2.bias"))
-                wgrad_side(Gi.dpre, Hd, A.h2[i], D, M, gv(b + "mlp.fc1.weight"), gv(b + "mlp.fc1.bias"))
-                wgrad_side(Gi.dxmb, D, A.o[i], D, M, gv(b + "attn.proj.weight"), gv(b + "attn.proj.bias"))
-                wgrad_side(Gi.dqkv, 3 * D, A.h1[i], D, M, gv(b + "attn.qkv.weight"), gv(b + "attn.qkv.bias"))
-                block_done(i)
-                continue
+                cap = functools.partial(self._capture_rows, i, M)
             R = self._bwd_rows(A, G, Gi, Gn, i, n)
             if prune and i == cfg.depth - 1:
                 # the last block on its CLS rows: MLP, LN2 and projection over n compact rows, then the CLS
                 # queries' attention backward into the full dqkv image; d(xmid) is Gi.dxm_cls
                 Rc, R.dxm = self._cls_rows(A, n, G=Gi), Gi.dxm_cls
-                ch.mlp_bwd(b, Rc, ln_bwd, wgrad_side)
-                ch.attn_bwd(b, R, ln_bwd, wgrad_side, before_ln1, cls=Rc, split_q=self.PRUNE_Q and n % 32 == 0)
+                ch.mlp_bwd(b, Rc, ln_bwd, sched.wgrad)
+                ch.attn_bwd(b, R, ln_bwd, sched.wgrad, before_ln1, cls=Rc, split_q=self.PRUNE_Q and n % 32 == 0)
             else:
                 # MLP: x_{i+1} = xmid + fc2(gelu(fc1(LN2(xmid)))), then attention: xmid = x_i + proj(attn(LN1(x_i)))
-                ch.mlp_bwd(b, R, ln_bwd, wgrad_side, cap, label="fc1_wgrad")
-                ch.attn_bwd(b, R, ln_bwd, wgrad_side, before_ln1, cap)
-            block_done(i)
+                ch.mlp_bwd(b, R, ln_bwd, sched.wgrad, cap, label="fc1_wgrad")
+                ch.attn_bwd(b, R, ln_bwd, sched.wgrad, before_ln1, cap)
+            if self.capture is not None:
+                self.capture("bwd", True, i, G.dx[:M])
+            sched.block_done(i)
         # ---- embedding: x_0 = [cls; patch_embed(img)] + pos
-        K0 = 3 * cfg.patch * cfg.patch
-        if lanes:
-            main.wait_stream(side)  # lane 1's rows of d(loss)/d(x_0)
         self._call("es_embed_bwd", ptr(G.dx), D, ptr(G.dpatch), D, ptr(gv("pos_embed")), ptr(gv("cls_token")), n, T, D, 0,
              s)
-        npat = n * cfg.np
-        wgrad_side(G.dpatch, D, A.patches, K0, npat, gv("patch_embed.proj.weight"), gv("patch_embed.proj.bias"))
-        flush_layer(-1)  # the patch-embedding weight gradient (layer_wg): the backward's last launch
-        if grouped:
-            self._launch_grouped(problems, 0)
-        if lnd:
-            self._ln_grads_flush(lnd)
-        if ov:
-            main.wait_stream(side)
-        if lanes:
-            main.wait_stream(third)
+        sched.wgrad(G.dpatch, D, A.patches, 3 * cfg.patch * cfg.patch, n * cfg.np, gv("patch_embed.proj.weight"),
+                    gv("patch_embed.proj.bias"))
+        sched.finish()  # the patch-embedding weight gradient is the backward's last launch
         return grad
 
-    def _bwd_rows(self, A, G, Gi, Gn, i, n, i0=0):
-        """Block i's reverse-pass row set over images [i0, i0 + n): its dY images in Gi (the weight gradients'
-        inputs), the bf16 d(block input) in Gn (the next block's), everything else in G."""
-        return Rows(n, self.cfg.T, self.cfg.heads, i0, dxb=Gi.dxb, pre=A.pre[i], act=A.act[i], dpre=Gi.dpre, dh=G.dh,
+    def _grad_sets(self, n, grouped):
+        """The backward scratch sets of batch size n (cached).  Two: layer i's weight-gradient inputs (dY images)
+        live in set i % 2, so the side stream can still read layer i+1's while the main stream writes layer i's.
+        grouped: one dY set per layer (+ a spare for layer 0's unused dY of the embedding), as the grouped launches
+        read several layers' weight-gradient inputs after the chain has moved on.  Set 0 is the same in both."""
+        mk = lambda: _Grads(self.cfg, n, self.device, self.op_dtype)  # noqa: E731
+        if n not in self._grads:
+            self._grads[n] = (mk(), mk())
+        if not grouped:
+            return self._grads[n]
+        key = (n, "grouped")
+        if key not in self._grads:
+            self._grads[key] = [self._grads[n][0]] + [mk() for _ in range(self.cfg.depth)]
+        return self._grads[key]
+
+    def _block_range(self, i):
+        """[lo, hi) of block i's (contiguous) parameters in the flat buffers."""
+        nxt = f"blocks.{i + 1}.norm1.weight" if i + 1 < self.cfg.depth else "norm.weight"
+        return self.offs[f"blocks.{i}.norm1.weight"], self.offs[nxt]
+
+    def _capture_rows(self, i, M, kind, *ts):
+        """The chain's test hook for block i of the reverse pass: the token rows of each tensor to self.capture."""
+        self.capture(kind, True, i, *(t[:M] for t in ts))
+
+    def _bwd_rows(self, A, G, Gi, Gn, i, n):
+        """Block i's reverse-pass row set: its dY images in Gi (the weight gradients' inputs), the bf16
+        d(block input) in Gn (the next block's), everything else in G."""
+        return Rows(n, self.cfg.T, self.cfg.heads, dxb=Gi.dxb, pre=A.pre[i], act=A.act[i], dpre=Gi.dpre, dh=G.dh,
                     h2=A.h2[i], xmid=A.xmid[i], mean2=A.mean2[i], rstd2=A.rstd2[i], dres=G.dx, dxm=G.dxm, dxmb=Gi.dxmb,
                     do=G.do, o=A.o[i], qkv=A.qkv[i], lse=A.lse[i], delta=G.delta, dqkv=Gi.dqkv, dh1=G.dh, h1=A.h1[i],
                     x=A.x[i], mean1=A.mean1[i], rstd1=A.rstd1[i], dx=G.dx, dxb_next=Gn.dxb)
-
-    def _lanes_block(self, ch, b, A, G, Gi, Gn, i, n, nh, main, side):
-        """Block i's data-gradient chain as two lanes (Engine.SHARD_LANES): images [0, nh) on the caller's
-        stream, [nh, n) on the side stream, each on its rows of the same buffers (token rows are per image, the
-        chain never mixes images).  The LayerNorm parameter gradients are the only sums over both halves: lane 1
-        adds its share to lane 0's (accumulate), ordered by an event.  Lane 0 finished block i+1 on main, lane 1
-        on side; the embedding backward waits for both."""
-        ev = {}
-        for ln, st in ((0, main), (1, side)):
-            i0, nl = (0, nh) if ln == 0 else (nh, n - nh)
-            which = iter(("ln2", "ln1"))
-
-            def ln_bwd(*a, ln=ln, st=st, which=which, **kw):
-                k = next(which)
-                if ln == 1:
-                    st.wait_event(ev[k])
-                self._ln_bwd(*a, lane=ln, accumulate=ln, **kw)
-                if ln == 0:
-                    ev[k] = st.record_event()
-            with torch.cuda.stream(st):
-                R = self._bwd_rows(A, G, Gi, Gn, i, nl, i0)
-                ch.mlp_bwd(b, R, ln_bwd)
-                ch.attn_bwd(b, R, ln_bwd)
 
     def _wgrad_layer(self, problems, layer):
         """One es_gemm_tn_big_grouped launch (+ its reduce) over a block's weight gradients, on the
@@ -836,11 +819,9 @@ class Engine:
         beside it; the first block's (the last launch of the backward: nothing left beside it) and the
         serial engine's to the whole chip.  The problem table travels in the kernel arguments (no
         host->device copy; capturable)."""
-        if self._ncu is None:
-            self._ncu = torch.cuda.get_device_properties(self.device).multi_processor_count
         share = self.LAYER_TN_SHARE if (self.overlap and layer > 0) else 1.0  # block 0 / the embedding: chip
-        target = max(1, int(self._ncu * share))
-        n, workspace = len(problems), lambda need: self.workspace(0)
+        target = max(1, int(self._ncu() * share))
+        n, workspace = len(problems), lambda need: self.workspace()
         pr = self.probe
         # probed at the launches sized like the timed ones: the CU-share-sized blocks (or every block of the
         # serial engine), not the first block's whole-chip launch at the end of an overlapped backward

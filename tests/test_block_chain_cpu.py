@@ -75,10 +75,10 @@ class Rig:
         launch()
 
     # the owner's callbacks, recorded in the same log
-    def ln_bwd(self, dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, M, lddx=None, accumulate=0):
+    def ln_bwd(self, dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, M, lddx=None):
         # the direct form of Engine._ln_bwd (vit.py:624-626) / of the Conformer (conformer.py:978-980, 1001-1003)
         block.layernorm_bwd(self.call, dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, self.t["ws_ln"], 1024, M, D,
-                            accumulate, lddx)
+                            0, lddx)
 
     def wgrad(self, dy, N1, x, N2, M, out, bias_out, ld1=None, ld2=None, label=None):
         self.log.append(("wgrad", dy.data_ptr(), N1, x.data_ptr(), N2, M, out.data_ptr(), bias_out.data_ptr(), ld1, ld2,
@@ -90,9 +90,9 @@ class Rig:
     def cap(self, kind, *ts):
         self.log.append(("cap", kind) + tuple(x.data_ptr() for x in ts))
 
-    def rows(self, i0=0, n=None):
+    def rows(self):
         t = self.t
-        return block.Rows(self.n if n is None else n, T, H, i0, x=t["x"], h1=t["h1"], mean1=t["mean1"], rstd1=t["rstd1"],
+        return block.Rows(self.n, T, H, x=t["x"], h1=t["h1"], mean1=t["mean1"], rstd1=t["rstd1"],
                           qkv=t["qkv"], o=t["o"], lse=t["lse"], xmid=t["xmid"], h2=t["h2"], mean2=t["mean2"],
                           rstd2=t["rstd2"], pre=t["pre"], act=t["act"], out=t["out"], dxb=t["dxb"], dpre=t["dpre"],
                           dh=t["dh"], dres=t["dx"], dxm=t["dxm"], dxmb=t["dxmb"], do=t["do"], delta=t["delta"],
@@ -207,51 +207,35 @@ def test_forward_cls_tail(split_q, monkeypatch):
         assert bool((r.t["c_h1"][:n] == 1).all()) and bool((r.t["c_h1"][n:] == 0).all())
 
 
-def exp_bwd_full(n, r0=0, i0=0, caps=True, lane=None, gelu_d=True):
-    """vit.py:853-887 (full rows) / vit.py:927-949 (a lane: rows from r0, images from i0, no callbacks)."""
+def exp_bwd_full(n, gelu_d=True):
+    """vit.py:853-887 (full rows)."""
     M = n * T
-    o2, o4 = r0 * 2, r0 * 4  # byte offsets of row r0 per column of a bf16 / fp32 buffer
-    acc = 0 if lane is None else lane
-    cb = lane is None
-    e = []
-    if caps:
-        e += [("cap", "b_dxb", P("dxb"))]  # vit.py:854
-    e += [("es_gemm_nt", MULAUX if gelu_d else DGELU, P("dxb", o2 * D), D, P("wt:mlp.fc2.weight"), D, None,
-           P("dpre", o2 * HD), HD, None, P("pre", o2 * HD), HD, M, HD, D, 0, S)]  # vit.py:855-856 / 927-929
-    if cb:  # vit.py:857
-        e += [("wgrad", P("dxb"), D, P("act"), HD, M, g("mlp.fc2.weight"), g("mlp.fc2.bias"), None, None, None)]
-    e += [("es_gemm_nt", BF16, P("dpre", o2 * HD), HD, P("wt:mlp.fc1.weight"), HD, None, P("dh", o2 * D), D, None, None, 0,
-           M, D, HD, 0, S)]  # vit.py:858-859 / 930-931 (EPI_DH = EPI_BF16: DH_BF16)
-    if cb:  # vit.py:860
-        e += [("wgrad", P("dpre"), HD, P("h2"), D, M, g("mlp.fc1.weight"), g("mlp.fc1.bias"), None, None, "fc1_wgrad")]
-    if caps:  # vit.py:862-863
-        e += [("cap", "b_dpre", P("dpre")), ("cap", "b_dh2", P("dh"))]
-    # vit.py:864-865 / 934-936 through Engine._ln_bwd's direct form, vit.py:625-626
-    e += [("es_layernorm_bwd_b16", P("dh", o2 * D), D, P("xmid", o4 * D), D, P("mean2", o4), P("rstd2", o4),
-           p("norm2.weight"), P("dx", o4 * D), D, P("dxm", o4 * D), D, P("dxmb", o2 * D), D, g("norm2.weight"),
-           g("norm2.bias"), P("ws_ln"), 1024, M, D, acc, S)]
-    e += [("es_gemm_nt", BF16, P("dxmb", o2 * D), D, P("wt:attn.proj.weight"), D, None, P("do", o2 * D), D, None, None, 0,
-           M, D, D, 0, S)]  # vit.py:867-868 / 939-940
-    if cb:  # vit.py:869
-        e += [("wgrad", P("dxmb"), D, P("o"), D, M, g("attn.proj.weight"), g("attn.proj.bias"), None, None, None)]
-    if caps:  # vit.py:871-872
-        e += [("cap", "b_dxm", P("dxm"), P("dxmb")), ("cap", "b_do", P("do"))]
-    e += [("es_attn_bwd", P("qkv", o2 * 3 * D), 3 * D, P("o", o2 * D), D, P("lse", i0 * H * T * 4),
-           P("delta", i0 * H * T * 4), P("do", o2 * D), D, P("dqkv", o2 * 3 * D), 3 * D, n, T, H, SCALE, S),
-          # vit.py:873-874 / 941-942
-          ("es_gemm_nt", BF16, P("dqkv", o2 * 3 * D), 3 * D, P("wt:attn.qkv.weight"), 3 * D, None, P("dh", o2 * D), D,
-           None, None, 0, M, D, 3 * D, 0, S)]  # vit.py:875-876 / 943-944
-    if cb:  # vit.py:877
-        e += [("wgrad", P("dqkv"), 3 * D, P("h1"), D, M, g("attn.qkv.weight"), g("attn.qkv.bias"), None, None, None)]
-    if caps:  # vit.py:879-880
-        e += [("cap", "b_dqkv", P("dqkv")), ("cap", "b_dh1", P("dh"))]
-    if cb:  # vit.py:881-885: flush_layer / done[i] / the wait on done[i + 1]
-        e += [("before_ln1",)]
-    # vit.py:886-887 / 947-949
-    e += [("es_layernorm_bwd_b16", P("dh", o2 * D), D, P("x", o4 * D), D, P("mean1", o4), P("rstd1", o4),
-           p("norm1.weight"), P("dxm", o4 * D), D, P("dx", o4 * D), D, P("dxb_next", o2 * D), D, g("norm1.weight"),
-           g("norm1.bias"), P("ws_ln"), 1024, M, D, acc, S)]
-    return e
+    return [
+        ("cap", "b_dxb", P("dxb")),  # vit.py:854
+        ("es_gemm_nt", MULAUX if gelu_d else DGELU, P("dxb"), D, P("wt:mlp.fc2.weight"), D, None, P("dpre"), HD, None,
+         P("pre"), HD, M, HD, D, 0, S),  # vit.py:855-856
+        ("wgrad", P("dxb"), D, P("act"), HD, M, g("mlp.fc2.weight"), g("mlp.fc2.bias"), None, None, None),  # vit.py:857
+        ("es_gemm_nt", BF16, P("dpre"), HD, P("wt:mlp.fc1.weight"), HD, None, P("dh"), D, None, None, 0, M, D, HD, 0,
+         S),  # vit.py:858-859 (EPI_DH = EPI_BF16: DH_BF16)
+        ("wgrad", P("dpre"), HD, P("h2"), D, M, g("mlp.fc1.weight"), g("mlp.fc1.bias"), None, None, "fc1_wgrad"),  # :860
+        ("cap", "b_dpre", P("dpre")), ("cap", "b_dh2", P("dh")),  # vit.py:862-863
+        # vit.py:864-865 through Engine._ln_bwd's direct form, vit.py:625-626
+        ("es_layernorm_bwd_b16", P("dh"), D, P("xmid"), D, P("mean2"), P("rstd2"), p("norm2.weight"), P("dx"), D,
+         P("dxm"), D, P("dxmb"), D, g("norm2.weight"), g("norm2.bias"), P("ws_ln"), 1024, M, D, 0, S),
+        ("es_gemm_nt", BF16, P("dxmb"), D, P("wt:attn.proj.weight"), D, None, P("do"), D, None, None, 0, M, D, D, 0,
+         S),  # vit.py:867-868
+        ("wgrad", P("dxmb"), D, P("o"), D, M, g("attn.proj.weight"), g("attn.proj.bias"), None, None, None),  # vit.py:869
+        ("cap", "b_dxm", P("dxm"), P("dxmb")), ("cap", "b_do", P("do")),  # vit.py:871-872
+        ("es_attn_bwd", P("qkv"), 3 * D, P("o"), D, P("lse"), P("delta"), P("do"), D, P("dqkv"), 3 * D, n, T, H, SCALE,
+         S),  # vit.py:873-874
+        ("es_gemm_nt", BF16, P("dqkv"), 3 * D, P("wt:attn.qkv.weight"), 3 * D, None, P("dh"), D, None, None, 0, M, D,
+         3 * D, 0, S),  # vit.py:875-876
+        ("wgrad", P("dqkv"), 3 * D, P("h1"), D, M, g("attn.qkv.weight"), g("attn.qkv.bias"), None, None, None),  # :877
+        ("cap", "b_dqkv", P("dqkv")), ("cap", "b_dh1", P("dh")),  # vit.py:879-880
+        ("before_ln1",),  # vit.py:881-885: flush_layer / done[i] / the wait on done[i + 1]
+        # vit.py:886-887
+        ("es_layernorm_bwd_b16", P("dh"), D, P("x"), D, P("mean1"), P("rstd1"), p("norm1.weight"), P("dxm"), D, P("dx"),
+         D, P("dxb_next"), D, g("norm1.weight"), g("norm1.bias"), P("ws_ln"), 1024, M, D, 0, S)]
 
 
 @pytest.mark.parametrize("gelu_d", [True, False])
@@ -262,18 +246,6 @@ def test_reverse_full_rows(gelu_d, monkeypatch):
     r.chain.mlp_bwd(BLK, R, r.ln_bwd, r.wgrad, r.cap, label="fc1_wgrad")
     r.chain.attn_bwd(BLK, R, r.ln_bwd, r.wgrad, r.before_ln1, r.cap)
     r.check(exp_bwd_full(n, gelu_d=gelu_d))
-
-
-def test_reverse_lane_with_row_offset(monkeypatch):
-    """Engine._lanes_block's lane 1 (vit.py:921-949): images [nh, n) on their rows of the same buffers, the
-    LayerNorm backwards with accumulate = the lane, no weight gradient recorded, no capture."""
-    n, nh = 5, 2
-    r = Rig(n, monkeypatch)
-    R = r.rows(i0=nh, n=n - nh)
-    ln_bwd = lambda *a, **kw: r.ln_bwd(*a, accumulate=1, **kw)  # noqa: E731
-    r.chain.mlp_bwd(BLK, R, ln_bwd)
-    r.chain.attn_bwd(BLK, R, ln_bwd)
-    r.check(exp_bwd_full(n - nh, r0=nh * T, i0=nh, caps=False, lane=1))
 
 
 @pytest.mark.parametrize("n", [32, 4])
