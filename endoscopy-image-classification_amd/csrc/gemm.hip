@@ -1829,6 +1829,10 @@ int es_gemm_nt(int epi, const void* A, int lda, const void* B, int ldb, const fl
       ((epi == EPI_F32_RESID || epi == EPI_DGELU || epi == EPI_MULAUX || epi == EPI_PATCH) && !aux))
     return ES_BAD_ARG;
   if (epi == EPI_PATCH && np <= 0) return ES_BAD_ARG;
+  // the epilogue reads aux in 16-B pieces at (m * ldaux + n): fp32 rows (residual, position table) a multiple of
+  // 4 elements, bf16 rows (pre-activation, GELU') of 8, and no row shorter than the N columns read from it
+  if ((epi == EPI_F32_RESID || epi == EPI_PATCH) && ((ldaux % 4) || ldaux < N)) return ES_BAD_SHAPE;
+  if ((epi == EPI_DGELU || epi == EPI_MULAUX) && ((ldaux % 8) || ldaux < N)) return ES_BAD_SHAPE;
   NTArgs a{(const bf16*)A, (const bf16*)B, bias, C, C2, aux, M, N, K, lda, ldb, ldc, ldaux, np};
   // variant -1 (default): per-shape choice measured on MI355X (scripts/gemm_bench.py, isolated launches at
   // the F1 shapes and at 1/2, 1/4, 1/8 of the batch -- a rank's share at N GPUs, --shard; r03 sweep with the

@@ -238,6 +238,15 @@ def call(name, *args):
     return rc
 
 
+def tn_variant():
+    """The process-wide es_gemm_tn pin in effect (-1: none): es_set_tn_variant returns the value it replaces, so the
+    pin is read by setting -1 and putting the old value back."""
+    lib = load()
+    v = lib.es_set_tn_variant(-1)
+    lib.es_set_tn_variant(v)
+    return v
+
+
 def ptr(t):
     """Device pointer of a tensor (None -> NULL).  Refuses CPU tensors: no CPU fallback exists."""
     if t is None:

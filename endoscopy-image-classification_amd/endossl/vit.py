@@ -633,6 +633,22 @@ class Engine:
         return (self.TN_SHARE < 1.0 and self.overlap and M >= self.TN_SHARE_MIN_M and N1 % 384 == 0
                 and N2 % 192 == 0 and self.precision == "bf16")
 
+    def _split_q_rows(self, n, tn_pin):
+        """Whether the pruned last block's Q weight gradient may run over the n CLS rows alone (rows img * T of dqkv
+        and h1, row strides T * 3 * D and T * D).  The weight-gradient kernels read whole token steps, and at these
+        strides the rows of a partial step lie past the token buffers (and are not the zero rows es_gemm_tn asks
+        for): n must fill the steps of the tile the launch lands on -- 32 rows on the 128 x 128 tile (and in the
+        grouped launch), 64 on the 384 x 192 tile.  That tile takes a D x D problem where D % 384 == 0 when it is
+        pinned (tn_pin 7: es_set_tn_variant / ENDOSSL_TN_VARIANT), and with no pin when the engine names it
+        (_tn_shared) or the library picks it (n >= 65536); a pin of 0 keeps it off.  bf16 engines only: the fp32
+        parity twin has no kernel variants."""
+        if n % 32:
+            return False
+        D = self.cfg.dim
+        big = self.precision == "bf16" and D % 384 == 0 and (
+            tn_pin == 7 or (tn_pin < 0 and (n >= 65536 or self._tn_shared(n, D, D))))
+        return n % 64 == 0 or not big
+
     def _wgrad(self, dy, N1, x, N2, M, out, bias_out=None, ld1=None, ld2=None, label=None):
         """out = dy^T x (weight grad) and, fused, bias_out = column sums of dy (row strides ld1 / ld2,
         default N1 / N2).  `label`: a launch site the bench can time with HIP events (self.probe)."""
@@ -765,7 +781,8 @@ class Engine:
                 # queries' attention backward into the full dqkv image; d(xmid) is Gi.dxm_cls
                 Rc, R.dxm = self._cls_rows(A, n, G=Gi), Gi.dxm_cls
                 ch.mlp_bwd(b, Rc, ln_bwd, sched.wgrad)
-                ch.attn_bwd(b, R, ln_bwd, sched.wgrad, before_ln1, cls=Rc, split_q=self.PRUNE_Q and n % 32 == 0)
+                split_q = self.PRUNE_Q and self._split_q_rows(n, _lib.tn_variant())
+                ch.attn_bwd(b, R, ln_bwd, sched.wgrad, before_ln1, cls=Rc, split_q=split_q)
             else:
                 # MLP: x_{i+1} = xmid + fc2(gelu(fc1(LN2(xmid)))), then attention: xmid = x_i + proj(attn(LN1(x_i)))
                 ch.mlp_bwd(b, R, ln_bwd, sched.wgrad, cap, label="fc1_wgrad")

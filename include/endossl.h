@@ -38,7 +38,9 @@ int es_abi_version(void);
  *   epi 7: C bf16 = GELU'(acc+bias), C2 bf16 = GELU(acc+bias)   (train fc1: keeps the derivative, not the
  *          pre-activation, so the backward needs no erf; activation bits identical to epi 1)
  *   epi 8: C bf16 = acc * aux bf16                     (fc2 dgrad times the stored GELU')
- * N % 128 == 0, K % 64 == 0; A readable for round_up(M,256) rows. */
+ * N % 128 == 0, K % 64 == 0; A readable for round_up(M,256) rows.  The epilogue reads aux in 16-byte pieces at
+ * (m * ldaux + n): -1 (ES_BAD_SHAPE) unless ldaux >= N and ldaux % 4 == 0 for the fp32 aux of epi 2 and 5,
+ * ldaux % 8 == 0 for the bf16 aux of epi 3 and 8 (ldaux is ignored by the other epilogues). */
 int es_gemm_nt(int epi, const void* A, int lda, const void* B, int ldb, const float* bias, void* C, int ldc,
                void* C2, const void* aux, int ldaux, int M, int N, int K, int np, hipStream_t stream);
 /* x = A B^T + bias + aux, h = LayerNorm(x; gamma, beta, eps) with per-row mean / rstd, in one launch, for
