@@ -351,15 +351,14 @@ __global__ __launch_bounds__(256) void cls_ln_fwd_kernel(const float* __restrict
   if (lane == 0) rstd_out[im] = rstd;
 }
 
-// dx_cls = LN'(dfts) into row img*T of dx (other rows untouched); dgamma / dbeta partials per
-// 4-image workgroup folded with fp32 atomics (the grad buffer is zeroed per step).
+// dx_cls = LN'(dfts) into row img*T of dx (other rows untouched); dgamma / dbeta come from
+// cls_ln_param_grads_kernel below.
 template <int V>
 __global__ __launch_bounds__(256) void cls_ln_bwd_kernel(const float* __restrict__ dfts, int lddf,
                                                          const float* __restrict__ gamma,
                                                          const float* __restrict__ xhat,
                                                          const float* __restrict__ rstd_in, float* __restrict__ dx,
-                                                         int lddx, int T, float* __restrict__ dgamma,
-                                                         float* __restrict__ dbeta, int n) {
+                                                         int lddx, int T, int n) {
   constexpr int D = V * 64;
   const int lane = threadIdx.x & 63;
   const int im = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -373,14 +372,47 @@ __global__ __launch_bounds__(256) void cls_ln_bwd_kernel(const float* __restrict
     gd[j] = dy[j] * gamma[d];
     s1 += gd[j];
     s2 += gd[j] * xh[j];
-    atomicAdd(dgamma + d, dy[j] * xh[j]);
-    atomicAdd(dbeta + d, dy[j]);
   }
   s1 = warp_sum(s1) * (1.0f / D);
   s2 = warp_sum(s2) * (1.0f / D);
   const float rstd = rstd_in[im];
 #pragma unroll
   for (int j = 0; j < V; ++j) dx[(size_t)im * T * lddx + j * 64 + lane] = rstd * (gd[j] - s1 - xh[j] * s2);
+}
+
+// dgamma[d] += sum_i dfts[i][d] xhat[i][d], dbeta[d] += sum_i dfts[i][d] (the grad buffer is zeroed per step).
+// One workgroup per 64 columns, 16 image slices (slice s takes images s, s + 16, ...): each thread sums its
+// slice in image order, thread 0..63 then add the 16 slices in slice order.  One writer per column, no atomics:
+// repeated launches give the same bits (fp32 atomics over the 4-image workgroups left the last bits of
+// norm.weight / norm.bias' gradients to the order the workgroups happened to run in).
+constexpr int CLS_LN_SLICES = 16;
+__global__ __launch_bounds__(CLS_LN_SLICES * 64) void cls_ln_param_grads_kernel(const float* __restrict__ dfts,
+                                                                                int lddf,
+                                                                                const float* __restrict__ xhat,
+                                                                                float* __restrict__ dgamma,
+                                                                                float* __restrict__ dbeta, int n,
+                                                                                int D) {
+  __shared__ float sg[CLS_LN_SLICES][64], sb[CLS_LN_SLICES][64];
+  const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
+  const int d = blockIdx.x * 64 + lane;  // D % 64 == 0: always a column
+  float ag = 0.f, ab = 0.f;
+  for (int i = sl; i < n; i += CLS_LN_SLICES) {
+    const float dy = dfts[(size_t)i * lddf + d];
+    ag = fmaf(dy, xhat[(size_t)i * D + d], ag);
+    ab += dy;
+  }
+  sg[sl][lane] = ag;
+  sb[sl][lane] = ab;
+  __syncthreads();
+  if (sl == 0) {
+    float g = 0.f, b = 0.f;
+    for (int k = 0; k < CLS_LN_SLICES; ++k) {
+      g += sg[k][lane];
+      b += sb[k][lane];
+    }
+    dgamma[d] += g;
+    dbeta[d] += b;
+  }
 }
 
 }  // namespace
@@ -492,7 +524,9 @@ int es_cls_ln_bwd(const float* dfts, int lddf, const float* gamma, const float* 
   if (n <= 0 || D % 64) return ES_BAD_SHAPE;
   if (!dfts || !gamma || !xhat || !rstd || !dx || !dgamma || !dbeta) return ES_BAD_ARG;
   const int grid = (n + 3) / 4;
-  HEAD_DISPATCH(cls_ln_bwd_kernel, D / 64, grid, stream, dfts, lddf, gamma, xhat, rstd, dx, lddx, T, dgamma, dbeta, n);
+  HEAD_DISPATCH(cls_ln_bwd_kernel, D / 64, grid, stream, dfts, lddf, gamma, xhat, rstd, dx, lddx, T, n);
+  hipLaunchKernelGGL(cls_ln_param_grads_kernel, D / 64, CLS_LN_SLICES * 64, 0, stream, dfts, lddf, xhat, dgamma, dbeta,
+                     n, D);
   return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
 }
 

@@ -96,6 +96,10 @@ SIGNATURES = {
     "es_softmax_predict": (I, [V, I, I, I, F, V, V, V, V]),
     "es_margin_softmax_workspace": (Z, [I, I]),
     "es_margin_softmax_fwd_bwd": (I, [V, I, V, V, V, V, V, I, I, I, I, F, F, F, F, V, I, V, V, V, V, V, V]),
+    "es_ezbm_sample_mix": (I, [V, I, V, I, I, I, V, V, V, V, U64, U64, V, V, I, V, I, V, V, V, V, V, V]),
+    "es_bn1d_groups_fwd": (I, [V, I, V, V, V, V, V, F, F, V, I, V, V, I, I, I, V]),
+    "es_bn1d_groups_bwd": (I, [V, I, V, V, V, V, I, V, V, I, I, I, V]),
+    "es_ezbm_ce_fwd_bwd": (I, [V, I, V, V, I, I, F, F, V, I, V, V]),
     "es_conv2d_fwd": (I, [V, I, I, I, I, L, L, L, L, V, V, I, I, I, I, I, V, L, L, L, I, V]),
     "es_conv2d_bwd_data": (I, [V, L, L, L, V, I, I, I, I, I, I, I, I, I, V, L, L, L, L, I, V]),
     "es_conv2d_dw_tiles": (I, [I, I, I, I]),

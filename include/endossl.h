@@ -218,7 +218,7 @@ int es_cls_head_bwd_ex(const float* dl, int lddl, const float* W, const float* g
 
 /* CoMatch features: fts [n, D] = LN(x_cls) (ModelwEmb's `fts` over the ViT trunk,
  * code/models/custom_model.py:207-209) and its backward into the CLS rows of dx; dgamma / dbeta
- * accumulated (+=). */
+ * accumulated (+=), the images summed in a fixed order (no atomics: repeated launches give the same bits). */
 int es_cls_ln_fwd(const float* x, int ldx, int T, const float* gamma, const float* beta, float* fts, int ldf,
                   float* xhat, float* rstd, int n, int D, float eps, hipStream_t stream);
 int es_cls_ln_bwd(const float* dfts, int lddf, const float* gamma, const float* xhat, const float* rstd, float* dx,
@@ -355,6 +355,45 @@ int es_margin_softmax_fwd_bwd(const float* x, int ldx, const float* W, const flo
                               const float* class_weights, const float* mask, int n, int F, int C, int kind, float s,
                               float m, float eps, float grad_scale, float* dx, int lddx, float* dW, float* db,
                               float* out, float* row_loss, float* workspace, hipStream_t stream);
+
+/* ---- EZBM stage 2 (code/ezbm.py:133-182; csrc/ezbm.hip) ------------------------------------------
+ * fp32, no atomics (repeated launches give the same bits), every output entry written.  A bad shape returns -1,
+ * a null required pointer -2, before any launch. */
+/* EmbFeatEZBM.__getitem__ (code/dataset.py:135-175) for n rows in one launch, and the mix of code/ezbm.py:162.
+ * mem [N, D] (row stride ldm) is the feature bank, mem_y [N] its int64 targets; cls_off [C+1] / cls_idx [N]
+ * (int32) list the bank rows by class (CSR, ascending within a class); cdf [C] is the dual draw's class CDF;
+ * lam_table [C*C] holds lam for (t, td).  Row i draws from the splitmix64 counter hash of es_dropout_keep at
+ * counters offset + 4i + k: k = 0 the row's class, ((z >> 40) * C) >> 24; k = 1 its member among the class's m
+ * rows, ((z >> 40) * m) >> 24; k = 2 the dual's class, the first c with (z >> 40) * 2^-24 < cdf[c] (the last
+ * class if none); k = 3 the dual's member.  With idx_in / dual_in (int32 [n], both or neither) nothing is drawn:
+ * those rows are used, and cls_off / cls_idx / cdf may be NULL.
+ * Out: X [2n, D] (row stride ldx): X[i] = mem[idx_i], X[n+i] = lam_i * mem[idx_i] + (1 - lam_i) * mem[dual_i]
+ * in torch's fp32 rounding (two rounded products, one rounded sum; 1 - lam_i rounded once); t / td [n] int64 =
+ * mem_y[idx] / mem_y[dual]; lam [n] = lam_table[t * C + td]; idx / dual [n] int32 the rows used.  A row index
+ * outside [0, N) (a bad replay index, an empty class) reads nothing: NaN rows, targets -1; a stored target
+ * outside [0, C) gives lam = NaN.  1 <= D <= 2048, 1 <= C <= 64, 1 <= N < 2^24, ldm / ldx >= D. */
+int es_ezbm_sample_mix(const float* mem, int ldm, const int64_t* mem_y, int N, int D, int C, const int* cls_off,
+                       const int* cls_idx, const float* cdf, const float* lam_table, unsigned long long seed,
+                       unsigned long long offset, const int* idx_in, const int* dual_in, int n, float* X, int ldx,
+                       int64_t* t, int64_t* td, float* lam, int* idx, int* dual, hipStream_t stream);
+/* BatchNorm1d in train mode over G consecutive groups of n rows (U [G*n, F]): each group normalised with its own
+ * batch mean / biased variance; the running buffers updated G times in group order (momentum, unbiased
+ * variance), num_batches_tracked (nullable) += G; xhat [G*n, F] and rstd [G, F] saved.  The backward gives each
+ * group's dU from that group's own sums; dgamma / dbeta = the groups' sums added in group order (overwritten).
+ * G = 1 is es_bn1d_fwd / es_bn1d_bwd bit for bit.  n >= 2, G >= 1, row strides >= F. */
+int es_bn1d_groups_fwd(const float* U, int ldu, const float* gamma, const float* beta, float* running_mean,
+                       float* running_var, void* num_batches_tracked, float momentum, float eps, float* Y, int ldy,
+                       float* xhat, float* rstd, int n, int G, int F, hipStream_t stream);
+int es_bn1d_groups_bwd(const float* dY, int lddy, const float* xhat, const float* rstd, const float* gamma, float* dU,
+                       int lddu, float* dgamma, float* dbeta, int n, int G, int F, hipStream_t stream);
+/* code/ezbm.py:163-167 on logits [2n, C], rows [0, n) = outputs_o, [n, 2n) = outputs_s, int64 t / td [n]:
+ *   l_o = mean_i CE(o_i, t_i);  l_s = 0.5 mean_i CE(s_i, t_i) + 0.5 mean_i CE(s_i, td_i)   (plain means)
+ *   out = {l_o + lambda_c l_s, l_o, l_s}
+ *   dlogits[i]   = grad_scale (softmax(o_i) - e_t) / n
+ *   dlogits[n+i] = grad_scale lambda_c (softmax(s_i) - 0.5 e_t - 0.5 e_td) / n
+ * A t_i or td_i outside [0, C) gives a NaN loss and zero gradient rows i and n+i.  C >= 1, ldl / lddl >= C. */
+int es_ezbm_ce_fwd_bwd(const float* logits, int ldl, const int64_t* t, const int64_t* td, int n, int C, float lambda_c,
+                       float grad_scale, float* dlogits, int lddl, float* out, hipStream_t stream);
 
 /* ---- Conformer CNN branch (SemiFormer backbone, code/models/conformer.py:75-445) ---------------
  * fp32 NHWC maps with element strides; Conv2d groups = 1, weights in the reference layout
