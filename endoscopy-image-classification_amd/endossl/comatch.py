@@ -25,19 +25,19 @@ Reference behaviour kept on purpose: `train_one` walks the wh
 loader, and the labeled batch comes from a FRESH iterator every step (`next()` on the DataLoader
 raises, code/comatch.py:135-138), i.e. always its first batch.
 """
-import numpy as np
 import torch
 
 from . import _lib, dist
 from ._lib import call, ptr
-from .fixmatch import FixMatch, _next
-from .loss import ce_loss
-from .utils import AverageMeter, calculate_metrics
+from .fixmatch import FixMatch
+from .trainer import _restarting
 
 HIST_CAP = 32  # distribution-alignment history (code/comatch.py:169-170)
 
 
 class CoMatch(FixMatch):
+    EMA_BUFFERS = True  # the head's BatchNorm1d running statistics
+
     def __init__(self, model, opt_func="Adam", lr=1e-3, device='cpu'):
         super().__init__(model, opt_func=opt_func, lr=lr, device=device)
         # code/comatch.py:29-39
@@ -181,14 +181,7 @@ class CoMatch(FixMatch):
 
         gb = dist.GradBuckets(m.flat_grad) if world > 1 and self.overlap_allreduce else None
         m.backward_from(dl, dz, grad_ready=gb.ready if gb is not None else None, trunk=not frozen)
-        gscale = gb.finish() if gb is not None else dist.allreduce_sum_(m.flat_grad)
-        ema = self.ema_model
-        self.optimizer.step(ema_flat=ema.ema.flat if ema is not None else None,
-                            ema_decay=float(ema.decay) if ema is not None else 0.0, grad_scale=gscale)
-        if ema is not None:
-            ema.update_buffers(m)
-            ema.ema.mark_updated()
-        self._inflight.record()
+        self._finish_step(gb.finish() if gb is not None else None)
         return {"loss": stats[4], "lx": stats[0], "lu": stats[1], "lc": stats[2], "mask_mean": stats[3],
                 "pseudo_label": W["pl"], "mask": W["mask"], "probs": W["probs"], "probs_orig": W["probs_orig"],
                 "logits": logits, "fts": fts, "z": z}
@@ -196,40 +189,5 @@ class CoMatch(FixMatch):
     def train_one(self, epoch):
         """Whole unlabeled loader per epoch; the labeled batch from a fresh iterator each step, as
         the reference (code/comatch.py:131-138)."""
-        self.model.train()
-        summary_loss = AverageMeter()
-        pending = []
-        for batch_idx, unl in enumerate(self.train_unlabeled_dl):
-            lab = _next(iter(self.train_labeled_dl))
-            out = self.step((lab, unl))
-            if self.lr_scheduler is not None:
-                self.lr_scheduler.step_update(epoch * self.config.TRAIN.EVAL_STEP + batch_idx)
-            pending.append(out["loss"].detach().clone())
-        for v in pending:
-            summary_loss.update(v.item(), self.config.DATA.BATCH_SIZE)
-        return summary_loss
-
-    def evaluate_one(self, show_metric=False, show_report=False, show_cf_matrix=False):
-        """code/comatch.py:237-281: EMA (or live) model in eval mode, `outputs, _, _ = model(x)`."""
-        eval_model = self.ema_model.ema if self.config.TRAIN.USE_EMA else self.model
-        eval_model.eval()
-        summary_loss = AverageMeter()
-        outs, tgts = [], []
-        with torch.no_grad():
-            for images, targets in self.valid_dl:
-                images = images.to(self.model.flat.device, non_blocking=True)
-                targets = targets.to(self.model.flat.device, non_blocking=True)
-                outputs, _, _ = eval_model(images)
-                losses = ce_loss(outputs, targets, reduction='mean')
-                summary_loss.update(losses.item(), self.config.DATA.BATCH_SIZE)
-                outs.append(outputs.argmax(1).cpu().numpy())
-                tgts.append(targets.cpu().numpy())
-        pred, tgt = np.concatenate(outs), np.concatenate(tgts)
-        metric = calculate_metrics(pred, tgt, self.config)
-        if show_metric:
-            print('Metric:')
-            print(metric)
-        if show_report:
-            from sklearn.metrics import classification_report
-            print(classification_report(tgt, pred))
-        return summary_loss, metric
+        pairs = ((_restarting(self.train_labeled_dl, "labeled")(), unl) for unl in self.train_unlabeled_dl)
+        return self._train_steps(self.step, pairs, epoch * self.config.TRAIN.EVAL_STEP)

@@ -37,7 +37,7 @@ class EmbHeads:
             D, F, C, L = self.cfg.dim, self.cfg.dim // 4, self.cfg.num_classes, self.cfg.low_dim
             z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.device)  # noqa: E731
             self._bufs[n] = {
-                "u": z(n, F), "xhat": z(n, F), "rstd": z(F), "y": z(n, F), "logits": z(n, C),
+                "u": z(n, F), "xhat": z(n, F), "rstd": z(2, F), "y": z(n, F), "logits": z(n, C),  # rstd: a row per BN group
                 "e": z(n, 3 * L), "v": z(n, L), "z": z(n, L), "norm": z(n),
                 "dy": z(n, F), "du": z(n, F), "dv": z(n, L), "de": z(n, 3 * L), "dfts": z(n, D),
                 "ws": z(n * max(F, C, 3 * L, L)), "keep": torch.ones(n, F, dtype=torch.uint8, device=self.device),
@@ -47,15 +47,25 @@ class EmbHeads:
     def forward(self, view, bn, fts, keep, train):
         """view(name) -> parameter view; bn = (running_mean, running_var, num_batches_tracked);
         keep: uint8 [n, D/4] dropout keep-mask (train only).  Returns (logits, z) buffer views."""
+        return self.fc_forward(view, bn, fts, keep, train), self.emb_forward(view, fts)
+
+    def fc_forward(self, view, bn, x, keep, train, groups=1):
+        """`fc` on the rows x [n, D]: fc.0 + ReLU + Dropout -> BatchNorm1d -> fc.4; returns the logits buffer.
+        groups = 2 (EZBM stage 2, one process only): the first and the second n / 2 rows are two passes through
+        BatchNorm1d, each with its own batch statistics and its own update of the running buffers."""
         cfg, s = self.cfg, _lib.stream()
-        n, D = int(fts.shape[0]), cfg.dim
-        F, C, L = D // 4, cfg.num_classes, cfg.low_dim
+        n, D = int(x.shape[0]), cfg.dim
+        F, C = D // 4, cfg.num_classes
         b = self.bufs(n)
         kp = ptr(keep) if train else None
-        call("es_dense_fwd", ptr(fts), D, ptr(view("fc.0.weight")), ptr(view("fc.0.bias")), ptr(b["u"]), F, n, D, F, 1,
+        call("es_dense_fwd", ptr(x), D, ptr(view("fc.0.weight")), ptr(view("fc.0.bias")), ptr(b["u"]), F, n, D, F, 1,
              0.0, kp, 1.0 / (1.0 - DROP_P), s)
         world = dist.world_size()
-        if train and world > 1:
+        if groups > 1:
+            call("es_bn1d_groups_fwd", ptr(b["u"]), F, ptr(view("fc.3.weight")), ptr(view("fc.3.bias")), ptr(bn[0]),
+                 ptr(bn[1]), ptr(bn[2]), BN_MOMENTUM, BN_EPS, ptr(b["y"]), F, ptr(b["xhat"]), ptr(b["rstd"]),
+                 n // groups, groups, F, s)
+        elif train and world > 1:
             # SyncBatchNorm: batch statistics over every rank's rows (the one-process batch of the
             # reference); two all-reduces of F floats (sum, then the centred sum of squares)
             N = float(n * world)
@@ -72,25 +82,41 @@ class EmbHeads:
                  ptr(b["xhat"]), ptr(b["rstd"]), n, F, s)
         call("es_dense_fwd", ptr(b["y"]), F, ptr(view("fc.4.weight")), ptr(view("fc.4.bias")), ptr(b["logits"]), C, n,
              F, C, 0, 0.0, None, 1.0, s)
+        return b["logits"]
+
+    def emb_forward(self, view, fts):
+        """`head_emb` on the features: head_emb.0 + LeakyReLU -> head_emb.2 -> l2norm; returns the z buffer."""
+        cfg, s = self.cfg, _lib.stream()
+        n, D, L = int(fts.shape[0]), cfg.dim, cfg.low_dim
+        b = self.bufs(n)
         call("es_dense_fwd", ptr(fts), D, ptr(view("head_emb.0.weight")), ptr(view("head_emb.0.bias")), ptr(b["e"]),
              3 * L, n, D, 3 * L, 2, LEAKY_SLOPE, None, 1.0, s)
         call("es_dense_fwd", ptr(b["e"]), 3 * L, ptr(view("head_emb.2.weight")), ptr(view("head_emb.2.bias")),
              ptr(b["v"]), L, n, 3 * L, L, 0, 0.0, None, 1.0, s)
         call("es_l2norm_fwd", ptr(b["v"]), L, ptr(b["z"]), L, ptr(b["norm"]), n, L, s)
-        return b["logits"], b["z"]
+        return b["z"]
 
     def backward(self, view, gview, fts, keep, dlogits, dz):
         """dlogits [n, C], dz [n, L] -> head parameter grads (written through gview) and returns
         dfts [n, D].  Uses the activations of the last train forward."""
+        self.fc_backward(view, gview, fts, keep, dlogits)  # writes dfts,
+        return self.emb_backward(view, gview, fts, dz)     # adds to it
+
+    def fc_backward(self, view, gview, x, keep, dlogits, groups=1, want_dx=True):
+        """fc.4 -> BatchNorm1d -> fc.0 of the last train fc_forward(x, groups): `fc`'s parameter grads, and with
+        want_dx the dfts buffer overwritten with d/dx (returned)."""
         cfg, s = self.cfg, _lib.stream()
-        n, D = int(fts.shape[0]), cfg.dim
-        F, C, L = D // 4, cfg.num_classes, cfg.low_dim
+        n, D = int(x.shape[0]), cfg.dim
+        F, C = D // 4, cfg.num_classes
         b = self.bufs(n)
         ws = b["ws"]
         call("es_dense_bwd", ptr(dlogits), C, None, 0, 0, 0.0, None, 1.0, ptr(b["y"]), F, ptr(view("fc.4.weight")),
              ptr(b["dy"]), F, 0, ptr(gview("fc.4.weight")), ptr(gview("fc.4.bias")), n, F, C, ptr(ws), s)
         world = dist.world_size()
-        if world > 1:  # SyncBatchNorm backward: the global means of dY and dY * xhat
+        if groups > 1:
+            call("es_bn1d_groups_bwd", ptr(b["dy"]), F, ptr(b["xhat"]), ptr(b["rstd"]), ptr(view("fc.3.weight")),
+                 ptr(b["du"]), F, ptr(gview("fc.3.weight")), ptr(gview("fc.3.bias")), n // groups, groups, F, s)
+        elif world > 1:  # SyncBatchNorm backward: the global means of dY and dY * xhat
             call("es_bn1d_bwd_sums", ptr(b["dy"]), F, ptr(b["xhat"]), n, F, ptr(b["sbl"]), s)
             b["sb"].copy_(b["sbl"])
             dist.allreduce_inplace_(b["sb"])
@@ -100,9 +126,19 @@ class EmbHeads:
         else:
             call("es_bn1d_bwd", ptr(b["dy"]), F, ptr(b["xhat"]), ptr(b["rstd"]), ptr(view("fc.3.weight")), ptr(b["du"]),
                  F, ptr(gview("fc.3.weight")), ptr(gview("fc.3.bias")), n, F, s)
-        call("es_dense_bwd", ptr(b["du"]), F, ptr(b["u"]), F, 1, 0.0, ptr(keep), 1.0 / (1.0 - DROP_P), ptr(fts), D,
-             ptr(view("fc.0.weight")), ptr(b["dfts"]), D, 0, ptr(gview("fc.0.weight")), ptr(gview("fc.0.bias")), n, D,
-             F, ptr(ws), s)
+        dx = b["dfts"] if want_dx else None
+        call("es_dense_bwd", ptr(b["du"]), F, ptr(b["u"]), F, 1, 0.0, ptr(keep), 1.0 / (1.0 - DROP_P), ptr(x), D,
+             ptr(view("fc.0.weight")), ptr(dx), D if want_dx else 0, 0, ptr(gview("fc.0.weight")),
+             ptr(gview("fc.0.bias")), n, D, F, ptr(ws), s)
+        return dx
+
+    def emb_backward(self, view, gview, fts, dz):
+        """l2norm -> head_emb.2 -> head_emb.0: `head_emb`'s parameter grads; d/dfts is ADDED to the dfts buffer
+        (returned)."""
+        cfg, s = self.cfg, _lib.stream()
+        n, D, L = int(fts.shape[0]), cfg.dim, cfg.low_dim
+        b = self.bufs(n)
+        ws = b["ws"]
         call("es_l2norm_bwd", ptr(dz), L, ptr(b["z"]), L, ptr(b["norm"]), ptr(b["dv"]), L, n, L, s)
         call("es_dense_bwd", ptr(b["dv"]), L, None, 0, 0, 0.0, None, 1.0, ptr(b["e"]), 3 * L,
              ptr(view("head_emb.2.weight")), ptr(b["de"]), 3 * L, 0, ptr(gview("head_emb.2.weight")),

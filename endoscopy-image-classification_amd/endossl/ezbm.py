@@ -14,12 +14,13 @@ autograd:
   sample   es_ezbm_sample_mix: X [2n, D] = [mem[idx]; lam mem[idx] + (1 - lam) mem[dual]], t, td, lam
            (EmbFeatEZBM.__getitem__ for the whole batch: a uniform class then a uniform member for the row; the
            dual's class from the 'balance' / 'reverse' CDF; a counter hash, not Python's `random`)
-  fwd      es_dropout_keep [2n, F]; fc.0 + ReLU + Dropout over the 2n rows; es_bn1d_groups_fwd with G = 2 (the
-           `o` rows, then the `s` rows, each with its own batch statistics -- fc(inputs), then fc(mix)); fc.4
+  fwd      es_dropout_keep [2n, F]; EmbHeads.fc_forward with 2 BatchNorm groups: fc.0 + ReLU + Dropout over the 2n
+           rows; es_bn1d_groups_fwd with G = 2 (the `o` rows, then the `s` rows, each with its own batch statistics
+           -- fc(inputs), then fc(mix)); fc.4
   loss     es_ezbm_ce_fwd_bwd: l_o + LAMBDA_C * l_s and d/dlogits
-  bwd      es_dense_bwd fc.4 (dW over the 2n rows = the sum of both passes), es_bn1d_groups_bwd, es_dense_bwd fc.0
-           with dX = NULL
-  opt      SupLearning._finish_step: optimizer + EMA sweep, EMA of the BatchNorm buffers
+  bwd      EmbHeads.fc_backward, 2 groups, no dX: es_dense_bwd fc.4 (dW over the 2n rows = the sum of both passes),
+           es_bn1d_groups_bwd, es_dense_bwd fc.0 with dX = NULL
+  opt      Trainer._finish_step (trainer.py): optimizer + EMA sweep, EMA of the BatchNorm buffers
 
 The flat gradient outside `fc` is ZERO in stage 2: it is zeroed when stage 2 is set up and at the start of every
 stage-2 epoch, and a step overwrites `fc`'s six slices only.  The optimizer is rebuilt for stage 2 (zero
@@ -27,18 +28,15 @@ moments), so the sweep leaves every frozen parameter bit for bit unchanged.
 
 One process only: every rank would hold a different bank, so a world size above 1 raises NotImplementedError.
 """
-import math
-
 import numpy as np
 import torch
 
 from . import _lib, dist
 from ._lib import call, ptr
-from .comatch_model import BN_EPS, BN_MOMENTUM, DROP_P
 from .lr_scheduler import build_scheduler
 from .optimizer import build_optimizer
 from .supervised import SupLearning
-from .utils import AttrDict, AverageMeter, count_parameters
+from .utils import AttrDict, count_parameters
 
 EXPANSIONS = ("balance", "reverse")
 
@@ -177,20 +175,9 @@ class EZBM(SupLearning):
         return out
 
     def train_one_stage_1(self, epoch):
-        self.model.train()
-        summary_loss = AverageMeter()
-        num_steps = len(self.train_dl)
         self._bank_n = 0  # the bank holds the last epoch run (code/ezbm.py:86)
         self._tables = None
-        pending = []
-        for step, batch in enumerate(self.train_dl):
-            out = self.step_stage_1(batch)
-            if self.lr_scheduler is not None:
-                self.lr_scheduler.step_update(epoch * num_steps + step)
-            pending.append(out["loss"].detach().clone())
-        for v in pending:  # one host sync per epoch
-            summary_loss.update(v.item(), self.config.DATA.BATCH_SIZE)
-        return summary_loss
+        return self._train_steps(self.step_stage_1, self.train_dl, epoch * len(self.train_dl))
 
     # ------------------------------------------------------------------------------------ stage 2
     def _fc_param_count(self):
@@ -207,11 +194,6 @@ class EZBM(SupLearning):
         self.lr_scheduler = build_scheduler(config=self.config, optimizer=self.optimizer, n_iter_per_epoch=n_iter)
         self.model.flat_grad.zero_()
         self.stage = 2
-
-    def _flat_view(self, flat, name):
-        """The slice of a flat buffer (parameters or gradients) that holds parameter `name`."""
-        o = self.model.offs[name]
-        return flat[o:o + self.model.get_parameter(name).numel()]
 
     def _stage2_tables(self):
         """Class table, CDF and lam table of the current bank, on the device (one host copy of the bank's targets
@@ -230,11 +212,10 @@ class EZBM(SupLearning):
     def _stage2_workspace(self, n):
         if n not in self._s2ws:
             dev, cfg = self.model.flat.device, self.model.cfg
-            D, F, C = cfg.dim, cfg.dim // 4, cfg.num_classes
+            D, C = cfg.dim, cfg.num_classes
             e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
             self._s2ws[n] = {"X": e(2 * n, D), "t": e(n, dt=torch.int64), "td": e(n, dt=torch.int64), "lam": e(n),
-                             "idx": e(n, dt=torch.int32), "dual": e(n, dt=torch.int32), "rstd": e(2, F),
-                             "dl": e(2 * n, C)}
+                             "idx": e(n, dt=torch.int32), "dual": e(n, dt=torch.int32), "dl": e(2 * n, C)}
         return self._s2ws[n]
 
     def step_stage_2(self, n=None, idx=None, dual=None, drop_keep=None):
@@ -259,8 +240,8 @@ class EZBM(SupLearning):
         N = self._bank_n
         s = _lib.stream()
         W = self._stage2_workspace(n)
-        b = m.heads().bufs(2 * n)
-        view, gview = (lambda nm: self._flat_view(m.flat, nm)), (lambda nm: self._flat_view(m.flat_grad, nm))
+        heads, eng = m.heads(), m.engine()
+        view, gview = (lambda nm: eng.view(m.flat, nm)), (lambda nm: eng.view(m.flat_grad, nm))
         if idx is not None:
             idx_in = idx.to(dev, torch.int32).contiguous()
             dual_in = dual.to(dev, torch.int32).contiguous()
@@ -276,26 +257,14 @@ class EZBM(SupLearning):
         keep = m.dropout_keep(2 * n) if drop_keep is None else drop_keep.to(dev, torch.uint8).contiguous()
         if tuple(keep.shape) != (2 * n, F):
             raise ValueError(f"step_stage_2: drop_keep of shape {tuple(keep.shape)}, [{2 * n}, {F}] expected")
-        scale = 1.0 / (1.0 - DROP_P)
-        bn = m.bn_buffers()
-        call("es_dense_fwd", ptr(W["X"]), D, ptr(view("fc.0.weight")), ptr(view("fc.0.bias")), ptr(b["u"]), F, 2 * n, D,
-             F, 1, 0.0, ptr(keep), scale, s)
-        call("es_bn1d_groups_fwd", ptr(b["u"]), F, ptr(view("fc.3.weight")), ptr(view("fc.3.bias")), ptr(bn[0]),
-             ptr(bn[1]), ptr(bn[2]), BN_MOMENTUM, BN_EPS, ptr(b["y"]), F, ptr(b["xhat"]), ptr(W["rstd"]), n, 2, F, s)
-        call("es_dense_fwd", ptr(b["y"]), F, ptr(view("fc.4.weight")), ptr(view("fc.4.bias")), ptr(b["logits"]), C,
-             2 * n, F, C, 0, 0.0, None, 1.0, s)
+        # fc(inputs) and fc(mix) as the two BatchNorm groups of one pass over the 2n rows (comatch_model.EmbHeads)
+        logits = heads.fc_forward(view, m.bn_buffers(), W["X"], keep, train=True, groups=2)
         stats = torch.empty(3, dtype=torch.float32, device=dev)  # loss, l_o, l_s
-        call("es_ezbm_ce_fwd_bwd", ptr(b["logits"]), C, ptr(W["t"]), ptr(W["td"]), n, C, float(cfg.TRAIN.LAMBDA_C), 1.0,
+        call("es_ezbm_ce_fwd_bwd", ptr(logits), C, ptr(W["t"]), ptr(W["td"]), n, C, float(cfg.TRAIN.LAMBDA_C), 1.0,
              ptr(W["dl"]), C, ptr(stats), s)
-        call("es_dense_bwd", ptr(W["dl"]), C, None, 0, 0, 0.0, None, 1.0, ptr(b["y"]), F, ptr(view("fc.4.weight")),
-             ptr(b["dy"]), F, 0, ptr(gview("fc.4.weight")), ptr(gview("fc.4.bias")), 2 * n, F, C, ptr(b["ws"]), s)
-        call("es_bn1d_groups_bwd", ptr(b["dy"]), F, ptr(b["xhat"]), ptr(W["rstd"]), ptr(view("fc.3.weight")),
-             ptr(b["du"]), F, ptr(gview("fc.3.weight")), ptr(gview("fc.3.bias")), n, 2, F, s)
-        call("es_dense_bwd", ptr(b["du"]), F, ptr(b["u"]), F, 1, 0.0, ptr(keep), scale, ptr(W["X"]), D,
-             ptr(view("fc.0.weight")), None, 0, 0, ptr(gview("fc.0.weight")), ptr(gview("fc.0.bias")), 2 * n, D, F,
-             ptr(b["ws"]), s)
+        heads.fc_backward(view, gview, W["X"], keep, W["dl"], groups=2, want_dx=False)
         self._finish_step()
-        return {"loss": stats[0], "l_o": stats[1], "l_s": stats[2], "logits": b["logits"], "t": W["t"], "td": W["td"],
+        return {"loss": stats[0], "l_o": stats[1], "l_s": stats[2], "logits": logits, "t": W["t"], "td": W["td"],
                 "lam": W["lam"], "idx": W["idx"], "dual": W["dual"]}
 
     def train_one_stage_2(self, epoch):
@@ -303,22 +272,12 @@ class EZBM(SupLearning):
         reference's DataLoader over EmbFeatEZBM; its index is ignored by __getitem__, so only the sizes matter)."""
         if getattr(self, "stage", 1) != 2:
             self.setup_stage_2()
-        self.model.train()
         self.model.flat_grad.zero_()
-        summary_loss = AverageMeter()
         bsz = int(self.config.DATA.BATCH_SIZE) * int(self.config.DATA.MU)
         N = self._bank_n
         self._stage2_tables()
-        num_steps = math.ceil(N / bsz)
-        pending = []
-        for step in range(num_steps):
-            out = self.step_stage_2(n=min(bsz, N - step * bsz))
-            if self.lr_scheduler is not None:
-                self.lr_scheduler.step_update(epoch * num_steps + step)
-            pending.append(out["loss"].detach().clone())
-        for v in pending:  # one host sync per epoch
-            summary_loss.update(v.item(), bsz)
-        return summary_loss
+        sizes = [min(bsz, N - first) for first in range(0, N, bsz)]
+        return self._train_steps(lambda n: self.step_stage_2(n=n), sizes, epoch * len(sizes), weight=bsz)
 
     # ------------------------------------------------------------------------------------ checkpoints, fit
     def load_checkpoint(self, checkpoint_dir, is_train=False):
@@ -334,22 +293,6 @@ class EZBM(SupLearning):
     def _log(self, values):
         if self.wandb is not None:
             self.wandb.log(values)
-
-    def _track_best(self, valid_loss, f1, save):
-        """The reference's rule (code/ezbm.py:369-382,413-426): better in loss AND score -> new best (saved when
-        `save`); worse in either -> 1 towards the early stop (never reset); returns that increment."""
-        if self.best_valid_loss and self.best_valid_score:
-            if self.best_valid_loss > valid_loss and self.best_valid_score < f1:
-                self.best_valid_loss, self.best_valid_score = valid_loss, f1
-                if save and dist.rank() == 0:
-                    self.save_checkpoint(self.config.TRAIN.SAVE_CP)
-            elif self.best_valid_loss < valid_loss or self.best_valid_score > f1:
-                return 1
-            return 0
-        self.best_valid_loss, self.best_valid_score = valid_loss, f1
-        if save and dist.rank() == 0:
-            self.save_checkpoint(self.config.TRAIN.SAVE_CP)
-        return 0
 
     def fit(self):
         print('-' * 10, 'Stage 1', '-' * 10)

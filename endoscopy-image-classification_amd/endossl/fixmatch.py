@@ -19,28 +19,24 @@ benchmark times.  One step (code/fixmatch.py:91-131):
   opt    Adam + EMA in one sweep, then lr_scheduler.step_update           (:123-127)
 
 No `.item()` per step: losses stay on device and the AverageMeter is filled once per epoch.
+Set-up, the comm / opt tail (`_finish_step`), the loops' helpers and the checkpoints are trainer.Trainer's.
 """
 import os
-from datetime import date, datetime
 
-import numpy as np
 import torch
 
 from . import _lib, dist
 from ._lib import call, ptr
-from .ema import ModelEMA
 from .loss import ce_loss
-from .lr_scheduler import build_scheduler
-from .optimizer import build_optimizer
-from .throttle import StepThrottle
-from .utils import AverageMeter, balanced_class_weights, calculate_metrics
+from .trainer import Trainer, _next  # noqa: F401  (_next: imported from here by callers)
+from .utils import AverageMeter
 
 
-def _next(it):
-    return it.next() if hasattr(it, "next") else next(it)
+class FixMatch(Trainer):
+    INFLIGHT_DEPTH = 2        # the ViT engine keeps its activations in its own buffers (throttle.py)
+    EMA_BUFFERS = False       # NativeViT has no buffers; CoMatch's model has (BatchNorm1d)
+    CKPT_SIZE_SUFFIX = True   # code/fixmatch.py:181-202
 
-
-class FixMatch:
     # bucketed all-reduce overlapped with the backward (world > 1): opt-in, ENDOSSL_OVERLAP_AR=1.  Off by
     # default: unmeasured over RCCL here (one GPU per box), and the two-rank gloo rehearsal on one GPU
     # ran 1.1-3.7 s/step with it vs 92 ms without whenever the engine's second stream was on
@@ -48,27 +44,16 @@ class FixMatch:
     overlap_allreduce = os.environ.get("ENDOSSL_OVERLAP_AR", "0") == "1"
 
     def __init__(self, model, opt_func="Adam", lr=1e-3, device='cpu'):
-        self.model = model
-        self.opt_func = opt_func
-        self.device = device
-        self.model.to(self.device)
+        super().__init__(model, opt_func=opt_func, lr=lr, device=device)
         self.epoch_start = 1
-        self.best_valid_perf = None
         self._dlogits = None
         self._stats = None
-        self._inflight = StepThrottle(2)
-
-    def get_dataloader(self, train_dl, valid_dl, test_dl=None):
-        self.train_labeled_dl, self.train_unlabeled_dl = train_dl
-        self.valid_dl = valid_dl
-        self.test_dl = test_dl
 
     def _trainable_when_frozen(self):
         """The modules IS_FREEZE keeps trainable (code/fixmatch.py:45-48: `model.fc`)."""
         return [self.model.fc]
 
     def get_config(self, config):
-        self.config = config
         # code/fixmatch.py:40-52: IS_FREEZE trains `model.fc` only (timm ViT: the classifier head).  The
         # native step then runs both forwards in inference form (no saved activations) and the head's
         # backward alone (Engine.head_backward): the trunk gets exactly zero gradient and no update
@@ -78,20 +63,8 @@ class FixMatch:
         if self.frozen:
             for mod in self._trainable_when_frozen():
                 mod.requires_grad_(True)
-        # identical replicas on every rank before the first step
-        dist.broadcast_(self.model.flat)
-        self.model.mark_updated()
-        self.ema_model = ModelEMA(model=self.model, decay=config.TRAIN.EMA_DECAY, device=self.device) \
-            if config.TRAIN.USE_EMA else None
-        self.optimizer = build_optimizer(self.model, opt_func=self.opt_func, lr=config.TRAIN.BASE_LR)
-        self.lr_scheduler = build_scheduler(config=config, optimizer=self.optimizer,
-                                            n_iter_per_epoch=config.TRAIN.EVAL_STEP)
-        if config.TRAIN.CLS_WEIGHT:
-            df = self.train_labeled_dl.dataset.df
-            w = balanced_class_weights(df[config.DATA.TARGET_NAME])
-            self.class_weights = torch.tensor(w, dtype=torch.float).to(self.device)
-        else:
-            self.class_weights = None
+        self._setup_model(config)
+        self._setup_optim(config, config.TRAIN.EVAL_STEP, self.train_labeled_dl)
 
     # ------------------------------------------------------------------ the hot step
     # The forward / losses / backward of a step as one hipGraph (torch.cuda.CUDAGraph over the C-ABI
@@ -187,100 +160,38 @@ class FixMatch:
             stats = self._run_graph(inputs)
         else:
             stats, gb = self._compute(*inputs)
-        gscale = gb.finish() if gb is not None else dist.allreduce_sum_(m.flat_grad)
-        ema = self.ema_model
-        self.optimizer.step(ema_flat=ema.ema.flat if ema is not None else None,
-                            ema_decay=float(ema.decay) if ema is not None else 0.0, grad_scale=gscale)
-        if ema is not None:
-            ema.ema.mark_updated()
-        self._inflight.record()
+        self._finish_step(gb.finish() if gb is not None else None)
         return {"loss": stats[3], "lx": stats[0], "lu": stats[1], "mask_mean": stats[2],
                 "pseudo_label": self._pl, "mask": self._mask}
 
     def train_one(self, epoch):
-        self.model.train()
-        labeled_iter = iter(self.train_labeled_dl)
-        unlabeled_iter = iter(self.train_unlabeled_dl)
-        summary_loss = AverageMeter()
-        pending = []
-        for batch_idx in range(self.config.TRAIN.EVAL_STEP):
-            try:
-                lab = _next(labeled_iter)
-            except StopIteration:
-                labeled_iter = iter(self.train_labeled_dl)
-                lab = _next(labeled_iter)
-            try:
-                unl = _next(unlabeled_iter)
-            except StopIteration:
-                unlabeled_iter = iter(self.train_unlabeled_dl)
-                unl = _next(unlabeled_iter)
-            out = self.step((lab, unl))
-            if self.lr_scheduler is not None:
-                self.lr_scheduler.step_update(epoch * self.config.TRAIN.EVAL_STEP + batch_idx)
-            pending.append(out["loss"].detach().clone())
-        for v in pending:  # one host sync per epoch instead of one per step (code/fixmatch.py:130)
-            summary_loss.update(v.item(), self.config.DATA.BATCH_SIZE)
-        return summary_loss
+        n = self.config.TRAIN.EVAL_STEP
+        return self._train_steps(self.step, self._paired_batches(n), epoch * n)
 
     def evaluate_one(self, show_metric=False, show_report=False, show_cf_matrix=False):
-        eval_model = self.ema_model.ema if self.config.TRAIN.USE_EMA else self.model
-        eval_model.eval()
+        """EMA (or live) model in eval mode; CoMatch's model returns (logits, fts, z) (code/comatch.py:237-281)."""
+        eval_model = self._eval_model()
         summary_loss = AverageMeter()
         outs, tgts = [], []
         with torch.no_grad():
             for images, targets in self.valid_dl:
                 images = images.to(self.model.flat.device, non_blocking=True)
                 targets = targets.to(self.model.flat.device, non_blocking=True)
-                outputs = eval_model(images)
+                outputs = self._first(eval_model(images))
                 losses = ce_loss(outputs, targets, reduction='mean')
                 summary_loss.update(losses.item(), self.config.DATA.BATCH_SIZE)
                 outs.append(outputs.argmax(1).cpu().numpy())
                 tgts.append(targets.cpu().numpy())
-        pred, tgt = np.concatenate(outs), np.concatenate(tgts)
-        metric = calculate_metrics(pred, tgt, self.config)
-        if show_metric:
-            print('Metric:')
-            print(metric)
-        if show_report:
-            from sklearn.metrics import classification_report
-            print(classification_report(tgt, pred))
-        return summary_loss, metric
+        return summary_loss, self._metrics(outs, tgts, show_metric, show_report)
 
-    def save_checkpoint(self, foldname):
-        """Same dict keys and filename scheme as code/fixmatch.py:181-202."""
-        checkpoint = {}
-        if self.config.TRAIN.USE_EMA:
-            checkpoint['ema_state_dict'] = self.ema_model.ema.state_dict()
-        d = date.today().strftime("%m_%d_%Y")
-        h = datetime.now().strftime("%H_%M_%S").split('_')
-        h[0] = str(int(h[0]) + 2)
-        filename = d + '_' + '_'.join(h) + '_epoch_' + str(self.epoch) + '_size_' + str(self.config.DATA.IMG_SIZE)
-        checkpoint['epoch'] = self.epoch
-        checkpoint['best_valid_perf'] = self.best_valid_perf
-        checkpoint['model_state_dict'] = self.model.state_dict()
-        checkpoint['optimizer'] = self.optimizer.state_dict()
-        checkpoint['scheduler'] = self.lr_scheduler.state_dict() if self.lr_scheduler is not None else {}
-        f = os.path.join(foldname, filename + '.pth')
-        torch.save(checkpoint, f)
-        print('Saved checkpoint')
-        return f
-
-    def load_checkpoint(self, checkpoint_dir, is_train=False):
-        checkpoint = torch.load(checkpoint_dir, map_location='cpu', weights_only=True)
-        self.model.load_state_dict(checkpoint['model_state_dict'])
-        # code/fixmatch.py:204-216: is_train -> trainable again (the IS_FREEZE split re-applied), else frozen
+    def _set_trainable(self, is_train):
+        """code/fixmatch.py:204-216: is_train -> trainable again (the IS_FREEZE split re-applied), else frozen."""
+        frozen = getattr(self, "frozen", False)
         for p in self.model.parameters():
-            p.requires_grad = bool(is_train) and not getattr(self, "frozen", False)
-        if is_train and getattr(self, "frozen", False):
+            p.requires_grad = bool(is_train) and not frozen
+        if is_train and frozen:
             for mod in self._trainable_when_frozen():
                 mod.requires_grad_(True)
-        if self.config.TRAIN.USE_EMA:
-            self.ema_model.ema.load_state_dict(checkpoint['ema_state_dict'])
-        self.epoch_start = checkpoint['epoch']
-        self.best_valid_perf = checkpoint['best_valid_perf']
-        self.optimizer.load_state_dict(checkpoint['optimizer'])
-        if self.lr_scheduler is not None:
-            self.lr_scheduler.load_state_dict(checkpoint['scheduler'])
 
     def fit(self):
         if self.epoch_start == self.config.TRAIN.EPOCHS:
@@ -289,17 +200,4 @@ class FixMatch:
             print(f'\tMetric: {valid_metric}')
             return
         for epoch in range(self.epoch_start, self.config.TRAIN.EPOCHS + 1):
-            self.epoch = epoch
-            lr = self.optimizer.param_groups[0]["lr"]
-            best = f"{float(self.best_valid_perf):.3f}" if self.best_valid_perf else "inf"
-            print(f'Training epoch: {self.epoch} | Current LR: {lr:.6f} | The best loss: {best}')
-            train_loss = self.train_one(self.epoch)
-            print(f'\tTrain Loss: {train_loss.avg:.3f}')
-            if epoch % self.config.TRAIN.FREQ_EVAL == 0 and self.valid_dl is not None:
-                valid_loss, valid_metric = self.evaluate_one()
-                if self.best_valid_perf is None or self.best_valid_perf > valid_loss.avg:
-                    self.best_valid_perf = valid_loss.avg
-                if dist.rank() == 0:
-                    self.save_checkpoint(self.config.TRAIN.SAVE_CP)
-                print(f'\tValid Loss: {valid_loss.avg:.3f}')
-                print(f'\tMetric: {valid_metric}')
+            self._fit_epoch(epoch)

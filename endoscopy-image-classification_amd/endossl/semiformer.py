@@ -12,47 +12,22 @@ save_checkpoint, load_checkpoint, fit -- plus `step(batch)` (one SSL step) and `
          losses = lx + LAMBDA_U * lu
   bwd    autograd over the HIP ops from d(losses)/d(logits) (weak rows: zero, detached)
   opt    Adam + EMA of the parameters in one sweep, EMA of the BatchNorm buffers, LR update
+         (trainer.Trainer._finish_step, as are set-up, checkpoints and the epoch body of `fit`)
 """
-import os
-from datetime import date, datetime
-
-import numpy as np
 import torch
 
-from . import _lib, dist
+from . import _lib
 from .conformer import join_wgrad_stream
 from ._lib import call, ptr
-from .ema import ModelEMA
-from .fixmatch import _next
 from .loss import weighted_ce_fwd_bwd
-from .lr_scheduler import build_scheduler
-from .optimizer import build_optimizer
-from .throttle import StepThrottle
-from .utils import AverageMeter, balanced_class_weights, calculate_metrics
+from .trainer import Trainer
+from .utils import AverageMeter
 
 
-class SemiFormer:
-    def __init__(self, model, opt_func="Adam", lr=1e-3, device='cpu'):
-        self.model = model
-        self.opt_func = opt_func
-        self.device = device
-        self.model.to(self.device)
-        self.epoch_start = 0
-        self.best_valid_perf = None
-        self._inflight = StepThrottle()
-
-    def get_dataloader(self, train_dl, valid_dl, test_dl=None):
-        self.train_labeled_dl, self.train_unlabeled_dl = train_dl
-        self.valid_dl = valid_dl
-        self.test_dl = test_dl
-
+class SemiFormer(Trainer):
     def get_config(self, config):
-        self.config = config
         print('Training mode: SemiFormer')
-        dist.broadcast_(self.model.flat)
-        self.model.mark_updated()
-        self.ema_model = ModelEMA(model=self.model, decay=config.TRAIN.EMA_DECAY, device=self.device) \
-            if config.TRAIN.USE_EMA else None
+        self._setup_model(config)
         # code/semiformer.py:50-56: IS_FREEZE trains conv_cls_head and trans_cls_head only; the native
         # forward then keeps the trunk off the autograd tape (NativeConformer.frozen_trunk) so only the
         # heads' backward runs, and the trunk's gradient stays exactly zero
@@ -63,15 +38,7 @@ class SemiFormer:
                 p.requires_grad = False
             self.model.conv_cls_head.requires_grad_(True)
             self.model.trans_cls_head.requires_grad_(True)
-        self.optimizer = build_optimizer(self.model, opt_func=self.opt_func, lr=config.TRAIN.BASE_LR)
-        self.lr_scheduler = build_scheduler(config=config, optimizer=self.optimizer,
-                                            n_iter_per_epoch=config.TRAIN.EVAL_STEP)
-        if config.TRAIN.CLS_WEIGHT:
-            df = self.train_labeled_dl.dataset.df
-            self.class_weights = torch.tensor(balanced_class_weights(df[config.DATA.TARGET_NAME]),
-                                              dtype=torch.float).to(self.device)
-        else:
-            self.class_weights = None
+        self._setup_optim(config, config.TRAIN.EVAL_STEP, self.train_labeled_dl)
 
     # ------------------------------------------------------------------ steps
     def _ce(self, logits, y, dl, out):
@@ -81,14 +48,7 @@ class SemiFormer:
         self.optimizer.zero_grad()
         torch.autograd.backward([out_conv, out_trans], [dconv, dtrans])
         join_wgrad_stream(self.model.flat.device)  # (the backward's final callback already did)
-        gscale = dist.allreduce_sum_(self.model.flat_grad)
-        ema = self.ema_model
-        self.optimizer.step(ema_flat=ema.ema.flat if ema is not None else None,
-                            ema_decay=float(ema.decay) if ema is not None else 0.0, grad_scale=gscale)
-        if ema is not None:
-            ema.update_buffers(self.model)
-            ema.ema.mark_updated()
-        self._inflight.record()
+        self._finish_step()
 
     def step(self, batch):
         """batch = ((x, y), ((u_w, u_s), idx)) -> dict of device scalars / tensors."""
@@ -139,40 +99,15 @@ class SemiFormer:
         return {"loss": stats.sum()}
 
     def train_one(self, epoch):
-        self.model.train()
-        summary_loss = AverageMeter()
-        pending = []
         if epoch < self.config.TRAIN.EVAL_STEP_SUP:
-            num_steps = len(self.train_labeled_dl)
-            for step, batch in enumerate(self.train_labeled_dl):
-                out = self.step_sup(batch)
-                self.lr_scheduler.step_update(epoch * num_steps + step)
-                pending.append(out["loss"].detach().clone())
-        else:
-            labeled_iter = iter(self.train_labeled_dl)
-            unlabeled_iter = iter(self.train_unlabeled_dl)
-            for batch_idx in range(self.config.TRAIN.EVAL_STEP):
-                try:
-                    lab = _next(labeled_iter)
-                except StopIteration:
-                    labeled_iter = iter(self.train_labeled_dl)
-                    lab = _next(labeled_iter)
-                try:
-                    unl = _next(unlabeled_iter)
-                except StopIteration:
-                    unlabeled_iter = iter(self.train_unlabeled_dl)
-                    unl = _next(unlabeled_iter)
-                out = self.step((lab, unl))
-                self.lr_scheduler.step_update(epoch * self.config.TRAIN.EVAL_STEP + batch_idx)
-                pending.append(out["loss"].detach().clone())
-        for v in pending:  # one host sync per epoch
-            summary_loss.update(v.item(), self.config.DATA.BATCH_SIZE)
-        return summary_loss
+            dl = self.train_labeled_dl
+            return self._train_steps(self.step_sup, dl, epoch * len(dl))
+        n = self.config.TRAIN.EVAL_STEP
+        return self._train_steps(self.step, self._paired_batches(n), epoch * n)
 
     def evaluate_one(self, show_metric=False, show_report=False, show_cf_matrix=False):
         """code/semiformer.py:150-198: CE of both heads, prediction = argmax softmax(conv + trans)."""
-        eval_model = self.ema_model.ema if self.config.TRAIN.USE_EMA else self.model
-        eval_model.eval()
+        eval_model = self._eval_model()
         summary_loss = AverageMeter()
         outs, tgts = [], []
         dev = self.model.flat.device
@@ -192,60 +127,8 @@ class SemiFormer:
                 # argmax of softmax(conv + trans) == argmax of (conv + trans)
                 outs.append((out_conv + out_trans).argmax(1).cpu().numpy())
                 tgts.append(targets.cpu().numpy())
-        pred, tgt = np.concatenate(outs), np.concatenate(tgts)
-        metric = calculate_metrics(pred, tgt, self.config)
-        if show_metric:
-            print('Metric:')
-            print(metric)
-        if show_report:
-            from sklearn.metrics import classification_report
-            print(classification_report(tgt, pred))
-        return summary_loss, metric
-
-    def save_checkpoint(self, foldname):
-        """Same dict keys and filename scheme as code/semiformer.py:201-221."""
-        checkpoint = {}
-        if self.config.TRAIN.USE_EMA:
-            checkpoint['ema_state_dict'] = self.ema_model.ema.state_dict()
-        d = date.today().strftime("%m_%d_%Y")
-        h = datetime.now().strftime("%H_%M_%S").split('_')
-        h[0] = str(int(h[0]) + 2)
-        filename = d + '_' + '_'.join(h) + '_epoch_' + str(self.epoch)
-        checkpoint['epoch'] = self.epoch
-        checkpoint['best_valid_perf'] = self.best_valid_perf
-        checkpoint['model_state_dict'] = self.model.state_dict()
-        checkpoint['optimizer'] = self.optimizer.state_dict()
-        checkpoint['scheduler'] = self.lr_scheduler.state_dict()
-        f = os.path.join(foldname, filename + '.pth')
-        torch.save(checkpoint, f)
-        print('Saved checkpoint')
-        return f
-
-    def load_checkpoint(self, checkpoint_dir, is_train=False):
-        checkpoint = torch.load(checkpoint_dir, map_location='cpu', weights_only=True)
-        self.model.load_state_dict(checkpoint['model_state_dict'])
-        for p in self.model.parameters():
-            p.requires_grad = bool(is_train)
-        if self.config.TRAIN.USE_EMA:
-            self.ema_model.ema.load_state_dict(checkpoint['ema_state_dict'])
-        self.epoch_start = checkpoint['epoch']
-        self.best_valid_perf = checkpoint['best_valid_perf']
-        self.optimizer.load_state_dict(checkpoint['optimizer'])
-        self.lr_scheduler.load_state_dict(checkpoint['scheduler'])
+        return summary_loss, self._metrics(outs, tgts, show_metric, show_report)
 
     def fit(self):
         for epoch in range(self.epoch_start, self.config.TRAIN.EPOCHS):
-            self.epoch = epoch
-            lr = self.optimizer.param_groups[0]["lr"]
-            best = f"{float(self.best_valid_perf):.3f}" if self.best_valid_perf else "inf"
-            print(f'Training epoch: {self.epoch} | Current LR: {lr:.6f} | The best loss: {best}')
-            train_loss = self.train_one(self.epoch)
-            print(f'\tTrain Loss: {train_loss.avg:.3f}')
-            if epoch % self.config.TRAIN.FREQ_EVAL == 0 and self.valid_dl is not None:
-                valid_loss, valid_metric = self.evaluate_one()
-                if self.best_valid_perf is None or self.best_valid_perf > valid_loss.avg:
-                    self.best_valid_perf = valid_loss.avg
-                if dist.rank() == 0:
-                    self.save_checkpoint(self.config.TRAIN.SAVE_CP)
-                print(f'\tValid Loss: {valid_loss.avg:.3f}')
-                print(f'\tMetric: {valid_metric}')
+            self._fit_epoch(epoch)

@@ -10,6 +10,7 @@ train_one, evaluate_one, save_checkpoint, load_checkpoint, fit -- plus `step(bat
          code/loss.py:118) -- value and d(loss)/d(logits) in one kernel (es_ce_weighted_fwd_bwd)
   bwd    autograd over the HIP ops
   opt    Adam + EMA of the parameters in one sweep, EMA of the BatchNorm buffers, LR update
+         (trainer.Trainer._finish_step; set-up and checkpoints are the base's too)
 
 The triplet mode (MODEL.IS_TRIPLET, :84-108) runs on the embedding-head ViT (comatch_model.NativeViTEmb) as
 a direct launch sequence, no autograd:
@@ -36,7 +37,6 @@ The mixup path is dead code in the reference (dataset.py always returns mixup_fn
 NotImplementedError.
 """
 import os
-from datetime import date, datetime
 
 import numpy as np
 import torch
@@ -44,12 +44,9 @@ import torch
 from . import _lib, dist
 from ._lib import call, ptr
 from .conformer import join_wgrad_stream
-from .ema import ModelEMA
 from .loss import AngularPenaltySMLoss, margin_softmax_fwd_bwd, weighted_ce_fwd_bwd
-from .lr_scheduler import build_scheduler
-from .optimizer import build_optimizer
-from .throttle import StepThrottle
-from .utils import AverageMeter, balanced_class_weights, calculate_metrics
+from .trainer import Trainer
+from .utils import AverageMeter
 
 
 class MarginModelError(ValueError, NotImplementedError):
@@ -57,17 +54,14 @@ class MarginModelError(ValueError, NotImplementedError):
     model, and -- as callers of the earlier, margin-less trainer caught it -- not implemented for it."""
 
 
-class SupLearning:
+class SupLearning(Trainer):
+    BEST_FIELDS = ("best_valid_loss", "best_valid_score")
+    RESTORE_BEST = False  # load_checkpoint (code/supervised.py:295) reads neither back
+    CKPT_PRINT = False
+
     def __init__(self, model, opt_func="Adam", lr=1e-3, device='cpu', wandb=None):
-        self.model = model
-        self.opt_func = opt_func
-        self.device = device
-        self.model.to(self.device)
-        self.epoch_start = 0
-        self.best_valid_loss = None
-        self.best_valid_score = None
+        super().__init__(model, opt_func=opt_func, lr=lr, device=device)
         self.wandb = wandb
-        self._inflight = StepThrottle()
 
     def get_dataloader(self, train_dl, valid_dl, mixup_fn=None, test_dl=None):
         self.train_dl = train_dl
@@ -78,7 +72,6 @@ class SupLearning:
         self.mixup_fn = None
 
     def get_config(self, config):
-        self.config = config
         print('Training mode: Supervised Learning')
         margin = str(getattr(config.MODEL, "MARGIN", "None")) != "None"
         self.is_triplet = bool(getattr(config.MODEL, "IS_TRIPLET", False))
@@ -96,19 +89,8 @@ class SupLearning:
         self.triplet_alpha = 0.7  # TripletLoss(alpha=0.7) (code/supervised.py:60)
         self.triplet_dist = {"d_ap": [], "d_an": []}
         self._tws = {}
-        dist.broadcast_(self.model.flat)
-        self.model.mark_updated()
-        self.ema_model = ModelEMA(model=self.model, decay=config.TRAIN.EMA_DECAY, device=self.device) \
-            if config.TRAIN.USE_EMA else None
-        self.optimizer = build_optimizer(self.model, opt_func=self.opt_func, lr=config.TRAIN.BASE_LR)
-        n_iter = len(self.train_dl) if self.train_dl is not None else 1
-        self.lr_scheduler = build_scheduler(config=config, optimizer=self.optimizer, n_iter_per_epoch=n_iter)
-        if config.TRAIN.CLS_WEIGHT:
-            df = self.train_dl.dataset.df
-            self.class_weights = torch.tensor(balanced_class_weights(df[config.DATA.TARGET_NAME]),
-                                              dtype=torch.float).to(self.device)
-        else:
-            self.class_weights = None
+        self._setup_model(config)
+        self._setup_optim(config, len(self.train_dl) if self.train_dl is not None else 1, self.train_dl)
 
     # The forward / loss / backward of a step as one hipGraph (torch.cuda.CUDAGraph over the C-ABI launches,
     # the conv weight-gradient side stream forked and joined inside): ResNet-18 at B=16 is host-bound eager
@@ -233,17 +215,6 @@ class SupLearning:
         self._finish_step()
         return {"loss": stats[0], "fts": x}
 
-    def _finish_step(self):
-        """Gradient all-reduce, optimizer + parameter EMA in one sweep, EMA of the BatchNorm buffers."""
-        gscale = dist.allreduce_sum_(self.model.flat_grad)
-        ema = self.ema_model
-        self.optimizer.step(ema_flat=ema.ema.flat if ema is not None else None,
-                            ema_decay=float(ema.decay) if ema is not None else 0.0, grad_scale=gscale)
-        if ema is not None:
-            ema.update_buffers(self.model)
-            ema.ema.mark_updated()
-        self._inflight.record()
-
     def step(self, batch, drop_keep=None):
         """batch = (images [n, 3, H, W], targets [n]) -> {"loss", "logits"} (device tensors); margin mode:
         {"loss", "fts"}.
@@ -269,32 +240,18 @@ class SupLearning:
         return {"loss": stats[0], "logits": logits.detach()}
 
     def train_one(self, epoch):
-        self.model.train()
-        summary_loss = AverageMeter()
-        num_steps = len(self.train_dl)
-        pending, dists = [], []
-        for step, batch in enumerate(self.train_dl):
+        dists = []
+
+        def step(batch):
             out = self.step(batch)
-            self.lr_scheduler.step_update(epoch * num_steps + step)
-            pending.append(out["loss"].detach().clone())
             if "d_ap" in out:  # triplet mode: the step's mean distances (code/supervised.py:99-100)
                 dists.append(torch.stack((out["d_ap"], out["d_an"])))
-        for v in pending:  # one host sync per epoch
-            summary_loss.update(v.item(), self.config.DATA.BATCH_SIZE)
+            return out
+        summary_loss = self._train_steps(step, self.train_dl, epoch * len(self.train_dl))
         if getattr(self, "is_triplet", False):
             d = torch.stack(dists).cpu().tolist() if dists else []
             self.triplet_dist = {"d_ap": [r[0] for r in d], "d_an": [r[1] for r in d]}
         return summary_loss
-
-    def _eval_model(self):
-        eval_model = self.ema_model.ema if self.config.TRAIN.USE_EMA else self.model
-        eval_model.eval()
-        return eval_model
-
-    @staticmethod
-    def _first(out):
-        """The logits of a model output: the first entry of ModelwEmb's (logits, fts, z)."""
-        return out[0] if isinstance(out, (tuple, list)) else out
 
     def evaluate_one(self, epoch=None, show_metric=False, show_report=False, show_cf_matrix=False):
         """code/supervised.py:148-196: unweighted CE mean, prediction = argmax softmax(logits)."""
@@ -313,15 +270,7 @@ class SupLearning:
                 summary_loss.update(st.item(), self.config.DATA.BATCH_SIZE)
                 outs.append(logits.argmax(1).cpu().numpy())
                 tgts.append(targets.cpu().numpy())
-        pred, tgt = np.concatenate(outs), np.concatenate(tgts)
-        metric = calculate_metrics(pred, tgt, self.config)
-        if show_metric:
-            print('Metric:')
-            print(metric)
-        if show_report:
-            from sklearn.metrics import classification_report
-            print(classification_report(tgt, pred))
-        return summary_loss, metric
+        return summary_loss, self._metrics(outs, tgts, show_metric, show_report)
 
     def _predict(self, logits, thres, want_label):
         """es_softmax_predict on a batch of logits -> int32 device tensor (argmax, or the thresholded label)."""
@@ -364,35 +313,22 @@ class SupLearning:
             return {}
         return dict(zip(index, torch.cat(labels).cpu().tolist()))
 
-    def save_checkpoint(self, foldname):
-        """Same dict keys and filename scheme as code/supervised.py:271-293."""
-        checkpoint = {}
-        if self.config.TRAIN.USE_EMA:
-            checkpoint['ema_state_dict'] = self.ema_model.ema.state_dict()
-        d = date.today().strftime("%m_%d_%Y")
-        h = datetime.now().strftime("%H_%M_%S").split('_')
-        h[0] = str(int(h[0]) + 2)
-        filename = d + '_' + '_'.join(h) + '_epoch_' + str(self.epoch)
-        checkpoint['epoch'] = self.epoch
-        checkpoint['best_valid_loss'] = self.best_valid_loss
-        checkpoint['best_valid_score'] = self.best_valid_score
-        checkpoint['model_state_dict'] = self.model.state_dict()
-        checkpoint['optimizer'] = self.optimizer.state_dict()
-        checkpoint['scheduler'] = self.lr_scheduler.state_dict()
-        f = os.path.join(foldname, filename + '.pth')
-        torch.save(checkpoint, f)
-        return f
-
-    def load_checkpoint(self, checkpoint_dir, is_train=False):
-        checkpoint = torch.load(checkpoint_dir, map_location='cpu', weights_only=True)
-        self.model.load_state_dict(checkpoint['model_state_dict'])
-        for p in self.model.parameters():
-            p.requires_grad = bool(is_train)
-        if self.config.TRAIN.USE_EMA:
-            self.ema_model.ema.load_state_dict(checkpoint['ema_state_dict'])
-        self.epoch_start = checkpoint['epoch']
-        self.optimizer.load_state_dict(checkpoint['optimizer'])
-        self.lr_scheduler.load_state_dict(checkpoint['scheduler'])
+    def _track_best(self, valid_loss, f1, save):
+        """The reference's rule (code/supervised.py:344-358, code/ezbm.py:369-382,413-426): better in loss AND score
+        -> new best (saved when `save`); worse in either -> 1 towards the early stop (never reset); returns that
+        increment."""
+        if self.best_valid_loss and self.best_valid_score:
+            if self.best_valid_loss > valid_loss and self.best_valid_score < f1:
+                self.best_valid_loss, self.best_valid_score = valid_loss, f1
+                if save and dist.rank() == 0:
+                    self.save_checkpoint(self.config.TRAIN.SAVE_CP)
+            elif self.best_valid_loss < valid_loss or self.best_valid_score > f1:
+                return 1
+            return 0
+        self.best_valid_loss, self.best_valid_score = valid_loss, f1
+        if save and dist.rank() == 0:
+            self.save_checkpoint(self.config.TRAIN.SAVE_CP)
+        return 0
 
     def fit(self):
         count_early_stop = 0
@@ -405,19 +341,6 @@ class SupLearning:
             print(f'\tTrain Loss: {train_loss.avg:.3f}')
             if epoch % self.config.TRAIN.FREQ_EVAL == 0 and self.valid_dl is not None:
                 valid_loss, valid_metric = self.evaluate_one(self.epoch)
-                f1 = float(valid_metric['macro/f1'])
-                # code/supervised.py:344-358: save on a better loss AND score, count the epochs that
-                # are worse in either (never reset, as in the reference)
-                if self.best_valid_loss and self.best_valid_score:
-                    if self.best_valid_loss > valid_loss.avg and self.best_valid_score < f1:
-                        self.best_valid_loss, self.best_valid_score = valid_loss.avg, f1
-                        if dist.rank() == 0:
-                            self.save_checkpoint(self.config.TRAIN.SAVE_CP)
-                    elif self.best_valid_loss < valid_loss.avg or self.best_valid_score > f1:
-                        count_early_stop += 1
-                else:
-                    self.best_valid_loss, self.best_valid_score = valid_loss.avg, f1
-                    if dist.rank() == 0:
-                        self.save_checkpoint(self.config.TRAIN.SAVE_CP)
+                count_early_stop += self._track_best(valid_loss.avg, float(valid_metric['macro/f1']), save=True)
                 print(f'\tValid Loss: {valid_loss.avg:.3f}')
                 print(f'\tMetric: {valid_metric}')

@@ -1,6 +1,6 @@
 """EZBM stage-2 step timing at ViT-S/16's head (D = 384, F = 96, C = 6, n = 192 rows: the published config's
 32 x 6), Adam + EMA, and how much of that step is the optimizer + EMA sweep over the whole flat buffer
-(SupLearning._finish_step alone, on the same trainer): the two alternated sample by sample in one process (device
+(the trainer's _finish_step alone, on the same trainer): the two alternated sample by sample in one process (device
 events around `--iters` back-to-back calls per sample, `--rounds` samples each after a warm-up), median / p10 /
 p90.  The bank lives on the device (random features, every class present); the trunk is never run.
   python scripts/ezbm_bench.py [--rounds 40] [--iters 10] [--out profiles/ezbm_stage2.txt]"""

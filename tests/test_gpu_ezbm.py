@@ -430,7 +430,7 @@ def test_stage2_step_vs_reference_fixture(exp):
             rec[f"s{s}/{k}"] = [o[k].item(), fx[f"s{s}/{k}"], abs(o[k].item() - fx[f"s{s}/{k}"]) / abs(fx[f"s{s}/{k}"])]
         sd1, esd = m.state_dict(), tr.ema_model.ema.state_dict()
         for k in er.FC_KEYS:
-            g = tr._flat_view(m.flat_grad, "fc." + k).cpu().view(fx[f"s{s}/grad/{k}"].shape)
+            g = m.engine().view(m.flat_grad, "fc." + k).cpu().view(fx[f"s{s}/grad/{k}"].shape)
             checks.append((f"s{s}/grad/{k}", g, fx[f"s{s}/grad/{k}"]))
         for k in er.FC_KEYS + er.BN_KEYS[:2]:
             checks.append((f"s{s}/param/{k}", sd1["fc." + k].cpu(), fx[f"s{s}/param/{k}"]))
