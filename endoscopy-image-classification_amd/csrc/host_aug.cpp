@@ -28,6 +28,8 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/endossl_aug_plan.h"
+
 namespace {
 
 using u8 = uint8_t;
@@ -797,6 +799,123 @@ void to_chw(const Img& im, u8* dst) {  // planar [3][S][S]
     for (int c = 0; c < 3; ++c) dst[c * n + i] = im.px[i * 3 + c];
 }
 
+// ---- the device input path's plan (include/endossl_aug_plan.h) --------------------------------------
+// The strong chain of fixmatch_pair with every draw and every double-precision parameter resolved into an
+// EsAugEntry; the pixels are then produced by csrc/device_aug.hip.  The draw order below DUPLICATES
+// fixmatch_pair / randaugment_mc / cutout_abs (tests/test_device_aug_cpu.py replays the plans against
+// esh_transform_batch); the parameter formulas duplicate apply_op / rotate / affine_nearest.
+bool resolve_op(EsAugOp& o, int op, int v, bool applied, bool neg, int S) {
+  std::memset(&o, 0, sizeof o);
+  o.op = op;
+  o.v = v;
+  o.applied = applied ? 1 : 0;
+  o.neg = applied && neg ? 1 : 0;
+  o.kind = ES_AUG_NONE;
+  o.alpha = 1.0f;
+  if (!applied) return true;
+  const double mx = POOL_MAX[op], bias = POOL_BIAS[op];
+  double m[6] = {1, 0, 0, 0, 1, 0};
+  bool affine = false;
+  switch (op) {
+    case OP_AUTOCONTRAST: case OP_EQUALIZE: o.kind = op; break;
+    case OP_BRIGHTNESS: case OP_COLOR: case OP_CONTRAST: case OP_SHARPNESS:
+      o.alpha = (float)(float_param(v, mx) + bias);
+      if (o.alpha != 1.0f) o.kind = op;  // Image.blend returns the image itself at 1.0
+      break;
+    case OP_IDENTITY: break;
+    case OP_POSTERIZE: {
+      const int bits = int_param(v, mx) + (int)bias;
+      o.mask = ~((1 << (8 - bits)) - 1) & 255;
+      o.kind = op;
+      break;
+    }
+    case OP_SOLARIZE:
+      o.thresh = 256 - (int_param(v, mx) + (int)bias);
+      o.kind = op;
+      break;
+    case OP_ROTATE: {
+      const int a = int_param(v, mx) + (int)bias;
+      double angle = std::fmod((double)(neg ? -a : a), 360.0);
+      if (angle < 0) angle += 360.0;
+      if (angle == 0.0) break;
+      if (angle == 90.0 || angle == 180.0 || angle == 270.0) return false;  // Pillow's transposes: not in the pool's range
+      const double cx = S / 2.0, cy = S / 2.0;
+      const double r = -(angle * (M_PI / 180.0));
+      m[0] = py_round15(std::cos(r));
+      m[1] = py_round15(std::sin(r));
+      m[3] = py_round15(-std::sin(r));
+      m[4] = py_round15(std::cos(r));
+      const double tx = m[0] * (-cx) + m[1] * (-cy) + 0.0, ty = m[3] * (-cx) + m[4] * (-cy) + 0.0;
+      m[2] = tx + cx;
+      m[5] = ty + cy;
+      affine = true;
+      break;
+    }
+    case OP_SHEARX: case OP_SHEARY: {
+      double s = float_param(v, mx) + bias;
+      if (neg) s = -s;
+      m[op == OP_SHEARX ? 1 : 3] = s;
+      affine = true;
+      break;
+    }
+    case OP_TRANSLATEX: case OP_TRANSLATEY: {
+      double f = float_param(v, mx) + bias;
+      if (neg) f = -f;
+      m[op == OP_TRANSLATEX ? 2 : 5] = (double)(int)(f * S);
+      affine = true;
+      break;
+    }
+    default: return false;
+  }
+  if (!affine) return true;
+  if (m[1] == 0.0 && m[3] == 0.0) {
+    // ImagingScaleAffine with a0 == a4 == 1 and whole offsets: column x reads (int)(t + 0.5 + x) = x + t
+    o.kind = ES_AUG_SHIFT;
+    o.shift_x = (int)m[2];
+    o.shift_y = (int)m[5];
+    return true;
+  }
+  auto fix = [](double q) { return (int)std::floor(q * 65536.0 + 0.5); };
+  o.kind = op;
+  o.a[0] = fix(m[0]);
+  o.a[1] = fix(m[1]);
+  o.a[3] = fix(m[3]);
+  o.a[4] = fix(m[4]);
+  o.a[2] = fix(m[2] + m[1] * 0.5 + m[0] * 0.5);
+  o.a[5] = fix(m[5] + m[4] * 0.5 + m[3] * 0.5);
+  return true;
+}
+
+bool plan_strong(EsAugEntry& e, int S, uint64_t seed) {
+  Rng rng(seed);
+  e.flip = rng.uniform() < 0.5 ? 1 : 0;
+  const int pad = (int)(S * 0.125);
+  e.top = rng.randint(0, 2 * pad + 1);
+  e.left = rng.randint(0, 2 * pad + 1);
+  int ops[2];
+  for (int i = 0; i < 2; ++i) ops[i] = rng.randint(0, OP_COUNT);
+  for (int i = 0; i < 2; ++i) {
+    const int v = rng.randint(1, 10);
+    const bool applied = rng.uniform() < 0.5;
+    const bool neg = applied ? rng.uniform() < 0.5 : false;  // the sign draw is made only when the op runs
+    if (!resolve_op(e.ops[i], ops[i], v, applied, neg, S)) return false;
+  }
+  const int cv = (int)(32 * 0.5);
+  const double fx = rng.uniform() * S, fy = rng.uniform() * S;
+  const int x0 = (int)std::max(0.0, fx - cv / 2.0), y0 = (int)std::max(0.0, fy - cv / 2.0);
+  e.rect[0] = x0;
+  e.rect[1] = y0;
+  e.rect[2] = (int)std::min((double)S, (double)x0 + cv);
+  e.rect[3] = (int)std::min((double)S, (double)y0 + cv);
+  return true;
+}
+
+// One (in -> out) table: bounds [out][2], then kk [out][ksize]
+struct PlanTable {
+  int in, out, ksize;
+  size_t off;
+};
+
 template <class F>
 void parallel_for(int n, int nthreads, F f) {
   if (nthreads <= 1 || n <= 1) {
@@ -924,6 +1043,112 @@ int esh_transform_batch(int kind, const uint8_t* const* srcs, const int* ws, con
       to_chw(out, out0 + per * i);
     }
   });
+  return ESH_OK;
+}
+
+// ---- the device input path's plan -----------------------------------------------------------------------
+int esh_aug_entry_size(void) { return (int)sizeof(EsAugEntry); }
+
+// The strong chain's entry fields (flip, top, left, two resolved op slots, the Cutout rectangle) from explicit
+// draws: ops / v / applied / neg hold two values each, rect four (x0, y0, x1, y1 as CutoutAbs passes them to
+// ImageDraw.rectangle).  The frame and resize fields of *entry are zeroed.
+int esh_aug_plan_from_draws(int S, int flip, int top, int left, const int* ops, const int* v, const int* applied,
+                            const int* neg, const int* rect, void* entry) {
+  if (!ops || !v || !applied || !neg || !rect || !entry) return ESH_BAD_ARG;
+  if (S < 2) return ESH_BAD_SHAPE;
+  const int pad = (int)(S * 0.125);
+  if (pad >= S || top < 0 || left < 0 || top > 2 * pad || left > 2 * pad) return ESH_BAD_SHAPE;
+  for (int i = 0; i < 2; ++i)
+    if (ops[i] < 0 || ops[i] >= OP_COUNT || v[i] < 0 || v[i] > 10) return ESH_BAD_ARG;
+  EsAugEntry e;
+  std::memset(&e, 0, sizeof e);
+  e.coef_h = e.coef_v = -1;
+  e.flip = flip != 0;
+  e.top = top;
+  e.left = left;
+  for (int i = 0; i < 2; ++i)
+    if (!resolve_op(e.ops[i], ops[i], v[i], applied[i] != 0, neg[i] != 0, S)) return ESH_BAD_ARG;
+  for (int i = 0; i < 4; ++i) e.rect[i] = rect[i];
+  std::memcpy(entry, &e, sizeof e);
+  return ESH_OK;
+}
+
+// The device path's frame arena: frames i = 0..n-1 (RGB HWC, ws[i] x hs[i]) copied back to back into arena on
+// nthreads host threads; frame_offs[i] receives frame i's byte offset and *arena_used the bytes written.
+// ESH_BAD_SHAPE (nothing copied, *arena_used = the bytes needed) when they exceed arena_cap.
+int esh_copy_frames(const uint8_t* const* srcs, const int* ws, const int* hs, int n, uint8_t* arena, size_t arena_cap,
+                    int64_t* frame_offs, size_t* arena_used, int nthreads) {
+  if (!srcs || !ws || !hs || n <= 0 || !arena || !frame_offs || !arena_used) return ESH_BAD_ARG;
+  size_t pos = 0;
+  for (int i = 0; i < n; ++i) {
+    if (bad_img(srcs[i], ws[i], hs[i])) return ESH_BAD_SHAPE;
+    frame_offs[i] = (int64_t)pos;
+    pos += (size_t)ws[i] * hs[i] * 3;
+  }
+  *arena_used = pos;
+  if (pos > arena_cap) return ESH_BAD_SHAPE;
+  parallel_for(n, nthreads, [&](int i) { std::memcpy(arena + frame_offs[i], srcs[i], (size_t)ws[i] * hs[i] * 3); });
+  return ESH_OK;
+}
+
+// The plan of esh_transform_batch(kind 0) for the same (seed, index): entries [n] (EsAugEntry), and Pillow's
+// 22-bit bilinear coefficient tables, one per distinct (in, out) size pair, appended to coeffs.  frame_offs[i] is
+// image i's byte offset in the caller's frame arena (NULL: the frames packed in order).  *coeff_used receives
+// the int32 count the tables take; when that exceeds coeff_cap (or coeffs is NULL) nothing is written to coeffs
+// and the call returns ESH_BAD_SHAPE, so a caller can size the buffer and call again.
+int esh_fixmatch_device_plan(const int* ws, const int* hs, const int64_t* frame_offs, int n, int S, int is_crop,
+                             uint64_t seed, void* entries, int32_t* coeffs, size_t coeff_cap, size_t* coeff_used) {
+  if (!ws || !hs || n <= 0 || !entries || !coeff_used) return ESH_BAD_ARG;
+  if (S < 2) return ESH_BAD_SHAPE;
+  const int R = is_crop ? (int)(S * 1.2) : S;
+  if (R < S || (int)(S * 0.125) >= S) return ESH_BAD_SHAPE;
+  for (int i = 0; i < n; ++i)
+    if (ws[i] <= 0 || hs[i] <= 0 || (frame_offs && frame_offs[i] < 0)) return ESH_BAD_SHAPE;
+  std::vector<PlanTable> tabs;
+  size_t used = 0;
+  auto table = [&](int in) -> const PlanTable& {
+    for (const PlanTable& t : tabs)
+      if (t.in == in) return t;
+    const double scale = (double)in / R;
+    const int ksize = (int)std::ceil(scale < 1.0 ? 1.0 : scale) * 2 + 1;  // precompute()'s
+    tabs.push_back(PlanTable{in, R, ksize, used});
+    used += (size_t)R * 2 + (size_t)R * ksize;
+    return tabs.back();
+  };
+  EsAugEntry* es = (EsAugEntry*)entries;
+  const int crop = is_crop ? py_round_half_even((R - S) / 2.0) : 0;
+  int64_t packed = 0;
+  for (int i = 0; i < n; ++i) {
+    EsAugEntry e;
+    std::memset(&e, 0, sizeof e);
+    e.frame_off = frame_offs ? frame_offs[i] : packed;
+    packed += (int64_t)ws[i] * hs[i] * 3;
+    e.w = ws[i];
+    e.h = hs[i];
+    e.coef_h = e.coef_v = -1;
+    if (e.w != R) {
+      const PlanTable& t = table(e.w);
+      e.coef_h = (int32_t)t.off;
+      e.ksize_h = t.ksize;
+    }
+    if (e.h != R) {
+      const PlanTable& t = table(e.h);
+      e.coef_v = (int32_t)t.off;
+      e.ksize_v = t.ksize;
+    }
+    e.crop = crop;
+    if (!plan_strong(e, S, image_seed(seed, (uint64_t)i, 0))) return ESH_BAD_ARG;
+    std::memcpy(&es[i], &e, sizeof e);
+  }
+  *coeff_used = used;
+  if (used > (size_t)INT32_MAX) return ESH_BAD_SHAPE;  // the entries hold 32-bit table offsets
+  if (!coeffs || used > coeff_cap) return ESH_BAD_SHAPE;
+  for (const PlanTable& t : tabs) {
+    const Coeffs c = precompute(t.in, t.out);
+    int32_t* dst = coeffs + t.off;
+    for (size_t k = 0; k < c.bounds.size(); ++k) dst[k] = c.bounds[k];
+    for (size_t k = 0; k < c.kk.size(); ++k) dst[c.bounds.size() + k] = c.kk[k];
+  }
   return ESH_OK;
 }
 

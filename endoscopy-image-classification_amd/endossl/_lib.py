@@ -190,6 +190,12 @@ SIGNATURES = {
     "es_embed_bwd_f32": (I, [V, I, V, I, V, V, I, I, I, I, V]),
     "es_pack_weights_f32": (I, [V, V, I, V]),
     "es_copy_f32": (I, [V, V, L, V]),
+    # the device input path (csrc/device_aug.hip; the plan comes from libendossl_host.so)
+    "es_aug_entry_size": (Z, []),
+    "es_aug_strong_workspace": (Z, [I, I]),
+    "es_aug_fixmatch_workspace": (Z, [I, I, I, I, I]),
+    "es_aug_fixmatch_u8": (I, [V, Z, V, V, Z, I, I, I, I, V, V, V, Z, V]),
+    "es_aug_strong_u8": (I, [V, V, I, I, V, V, Z, V]),
 }
 
 ABI_VERSION = 1

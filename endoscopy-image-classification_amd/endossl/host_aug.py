@@ -45,7 +45,33 @@ _SIG = {
     "esh_pad_reflect_crop": (_I, [_P, _I, _I, _I, _I, _I, _I, _P]),
     "esh_transform_batch": (_I, [_I, ctypes.POINTER(_P), ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _I, _I,
                                  ctypes.c_uint64, _I, _P, _P, _P]),
+    "esh_aug_entry_size": (_I, []),
+    "esh_aug_plan_from_draws": (_I, [_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I),
+                                     ctypes.POINTER(_I), ctypes.POINTER(_I), _P]),
+    "esh_copy_frames": (_I, [_P, _P, _P, _I, _P, ctypes.c_size_t, _P, ctypes.POINTER(ctypes.c_size_t), _I]),
+    "esh_fixmatch_device_plan": (_I, [_P, _P, _P, _I, _I, _I, ctypes.c_uint64, _P, _P, ctypes.c_size_t,
+                                      ctypes.POINTER(ctypes.c_size_t)]),
 }
+
+
+class AugOp(ctypes.Structure):
+    """EsAugOp (include/endossl_aug_plan.h): one RandAugmentMC slot with its parameters resolved."""
+    _fields_ = [("op", ctypes.c_int32), ("v", ctypes.c_int32), ("applied", ctypes.c_int32),
+                ("neg", ctypes.c_int32), ("kind", ctypes.c_int32),
+                ("alpha", ctypes.c_float), ("mask", ctypes.c_int32), ("thresh", ctypes.c_int32),
+                ("a", ctypes.c_int32 * 6), ("shift_x", ctypes.c_int32), ("shift_y", ctypes.c_int32)]
+
+
+class AugEntry(ctypes.Structure):
+    """EsAugEntry: one image's plan for the device input path."""
+    _fields_ = [("frame_off", ctypes.c_int64), ("w", ctypes.c_int32), ("h", ctypes.c_int32),
+                ("coef_h", ctypes.c_int32), ("ksize_h", ctypes.c_int32), ("coef_v", ctypes.c_int32),
+                ("ksize_v", ctypes.c_int32), ("crop", ctypes.c_int32), ("flip", ctypes.c_int32),
+                ("top", ctypes.c_int32), ("left", ctypes.c_int32), ("ops", AugOp * 2), ("rect", ctypes.c_int32 * 4)]
+
+
+ENTRY_BYTES = ctypes.sizeof(AugEntry)
+AUG_NONE, AUG_SHIFT = 5, 14  # EsAugOp.kind beside the pool indices
 _lib = None
 _lock = threading.Lock()
 
@@ -67,6 +93,9 @@ def load():
                 fn.restype, fn.argtypes = res, args
             if lib.esh_abi_version() != ABI_VERSION:
                 raise HostLibraryError(f"host ABI {lib.esh_abi_version()} != {ABI_VERSION}")
+            if lib.esh_aug_entry_size() != ENTRY_BYTES:
+                raise HostLibraryError(f"EsAugEntry is {lib.esh_aug_entry_size()} bytes in the host library, "
+                                       f"{ENTRY_BYTES} in host_aug.AugEntry")
             _lib = lib
     return _lib
 
@@ -261,6 +290,258 @@ class HostBatcher:
             cur.wait_stream(self._stream)
             for d in out:
                 d.record_stream(cur)
+        self.step += 1
+        self._submit(self.step)
+        return out
+
+
+# ---- the device input path: the plan on the host, the pixels on the GPU (csrc/device_aug.hip) ------------
+_dev = None
+
+
+def _device():
+    """libendossl_hip.so, once its EsAugEntry is known to be the host library's and this module's."""
+    global _dev
+    if _dev is None:
+        from . import _lib
+        lib = _lib.load()
+        load()
+        if lib.es_aug_entry_size() != ENTRY_BYTES:
+            raise HostLibraryError(f"EsAugEntry is {lib.es_aug_entry_size()} bytes in the device library, "
+                                   f"{ENTRY_BYTES} in the host library")
+        _dev = lib
+    return _dev
+
+
+def resize_side(size, is_crop=True):
+    """The side TransformFixMatch resizes to: int(1.2 S) before CenterCrop(S) with IS_CROP, else S."""
+    return int(size * 1.2) if is_crop else size
+
+
+def aug_plan_from_draws(size, flip, top, left, ops, v, applied, neg, rect):
+    """One AugEntry's strong-chain fields from explicit draws (two op slots; ops by name or pool index)."""
+    ops = [POOL.index(o) if isinstance(o, str) else int(o) for o in ops]
+    e = AugEntry()
+    arr = lambda xs, k: (_I * k)(*[int(x) for x in xs])  # noqa: E731
+    _check(load().esh_aug_plan_from_draws(int(size), int(flip), int(top), int(left), arr(ops, 2), arr(v, 2),
+                                          arr(applied, 2), arr(neg, 2), arr(rect, 4), ctypes.addressof(e)),
+           "esh_aug_plan_from_draws")
+    return e
+
+
+def fixmatch_device_plan(ws, hs, size, is_crop=True, seed=0, frame_offs=None, entries=None, coeffs=None):
+    """The plan of transform_batch(kind='fixmatch') for frames of sizes ws x hs and the same (seed, index).
+
+    Returns (entries, coeffs, used): entries a uint8 array [n, ENTRY_BYTES] (view it with
+    plan_entries()), coeffs an int32 array whose first `used` values are the resize tables.  `entries` /
+    `coeffs` may be preallocated (e.g. numpy views of pinned tensors); a coeffs buffer that is too small is
+    replaced by a fresh array.  frame_offs: each frame's byte offset in the arena (default: packed in order)."""
+    ws = np.ascontiguousarray(ws, np.int32)
+    hs = np.ascontiguousarray(hs, np.int32)
+    n = len(ws)
+    if entries is None:
+        entries = np.zeros((n, ENTRY_BYTES), np.uint8)
+    if coeffs is None:
+        coeffs = np.zeros(4096, np.int32)
+    offs = None if frame_offs is None else np.ascontiguousarray(frame_offs, np.int64)
+    used = ctypes.c_size_t()
+    lib = load()
+    for _ in range(2):
+        rc = lib.esh_fixmatch_device_plan(_ptr(ws), _ptr(hs), None if offs is None else _ptr(offs), n, int(size),
+                                          int(bool(is_crop)), int(seed) & (2 ** 64 - 1), _ptr(entries), _ptr(coeffs),
+                                          coeffs.size, ctypes.byref(used))
+        if rc == 3 and used.value > coeffs.size:  # sized by the refused call
+            coeffs = np.zeros(used.value, np.int32)
+            continue
+        break
+    _check(rc, "esh_fixmatch_device_plan")
+    return entries, coeffs, used.value
+
+
+def plan_entries(entries):
+    """A uint8 plan buffer as a ctypes array of AugEntry (sharing its memory)."""
+    n = entries.size // ENTRY_BYTES
+    return (AugEntry * n).from_buffer(entries)
+
+
+def _dev_u8(a, device):
+    return torch.from_numpy(a.view(np.uint8).reshape(-1)).to(device)
+
+
+def device_strong(weak, entries, workspace=None):
+    """The strong chain (flip -> reflect crop -> two ops -> Cutout) of a device uint8 [n, 3, S, S] batch
+    under explicit plans (a list of AugEntry or a plan buffer): es_aug_strong_u8."""
+    from . import _lib
+    lib = _device()
+    n, _, S, _ = weak.shape
+    if not isinstance(entries, np.ndarray):
+        entries = np.frombuffer(bytearray(b"".join(bytes(e) for e in entries)), np.uint8)
+    if entries.size != n * ENTRY_BYTES:
+        raise ValueError("one plan entry per image")
+    ent = _dev_u8(entries, weak.device)
+    nbytes = lib.es_aug_strong_workspace(n, S)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=weak.device)
+    strong = torch.empty_like(weak)
+    _lib.call("es_aug_strong_u8", _lib.ptr(weak.contiguous()), _lib.ptr(ent), n, S, _lib.ptr(strong),
+              _lib.ptr(workspace), workspace.numel(), _lib.stream())
+    return strong
+
+
+def _run_fixmatch(frames, frames_bytes, ent, coef, used, n, size, is_crop, max_h, want_strong, workspace, device):
+    """One es_aug_fixmatch_u8 call on the current stream over device buffers; returns the views."""
+    from . import _lib
+    weak = torch.empty((n, 3, size, size), dtype=torch.uint8, device=device)
+    strong = torch.empty_like(weak) if want_strong else None
+    _lib.call("es_aug_fixmatch_u8", _lib.ptr(frames), frames_bytes, _lib.ptr(ent), _lib.ptr(coef) if used else None,
+              used, n, size, int(bool(is_crop)), max_h, _lib.ptr(weak), _lib.ptr(strong), _lib.ptr(workspace),
+              workspace.numel(), _lib.stream())
+    return (weak, strong) if want_strong else (weak,)
+
+
+def device_transform_batch(images, size, kind="fixmatch", is_crop=True, seed=0, device="cuda"):
+    """transform_batch(kind='fixmatch' | 'eval') with the pixels made on the GPU: the frames are copied to the
+    device as they are, the host only builds the plan.  Returns device uint8 [n, 3, S, S] tensors, byte for
+    byte transform_batch's for the same seed."""
+    if kind not in ("fixmatch", "eval"):
+        raise ValueError("the device input path runs TransformFixMatch ('fixmatch') and its weak view ('eval')")
+    lib = _device()
+    arrs = [_hwc(im) for im in images]
+    n = len(arrs)
+    ws = [a.shape[1] for a in arrs]
+    hs = [a.shape[0] for a in arrs]
+    entries, coeffs, used = fixmatch_device_plan(ws, hs, size, is_crop, seed)
+    arena = np.concatenate([a.reshape(-1) for a in arrs])
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        nbytes = lib.es_aug_fixmatch_workspace(n, size, int(bool(is_crop)), max(ws), max(hs))
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        coef = torch.from_numpy(coeffs[:max(used, 1)]).to(dev)
+        return _run_fixmatch(torch.from_numpy(arena).to(dev), arena.size, _dev_u8(entries, dev), coef, used, n, size,
+                             is_crop, max(hs), kind == "fixmatch", workspace, dev)
+
+
+def plan_and_copy(images, ws, hs, idx, size, is_crop, seed, entries, coeffs, arena=None, offsets=None, threads=1):
+    """The host's whole share of one device-path batch: frames images[idx] copied back to back into `arena` on
+    `threads` host threads (or, with the frame set already on the device, `offsets` = every frame's offset
+    there) and the plan written into `entries` / `coeffs` (numpy views, e.g. of pinned tensors).  Returns
+    (arena bytes, coefficient count)."""
+    ws, hs = np.ascontiguousarray(ws[idx], np.int32), np.ascontiguousarray(hs[idx], np.int32)
+    if offsets is not None:
+        offs, pos = offsets[idx], 0
+    else:
+        ptrs = np.fromiter((images[i].ctypes.data for i in idx), np.uint64, len(idx))
+        offs = np.empty(len(idx), np.int64)
+        used = ctypes.c_size_t()
+        _check(load().esh_copy_frames(_ptr(ptrs), _ptr(ws), _ptr(hs), len(idx), _ptr(arena), arena.size, _ptr(offs),
+                                      ctypes.byref(used), int(threads)), "esh_copy_frames")
+        pos = used.value
+    _, out, used = fixmatch_device_plan(ws, hs, size, is_crop, seed=seed, frame_offs=offs, entries=entries,
+                                        coeffs=coeffs)
+    if out is not coeffs:
+        raise ValueError(f"coefficient buffer of {coeffs.size} int32 is too small: {used} needed")
+    return pos, used
+
+
+class DeviceBatcher:
+    """HostBatcher's contract (constructor, _indices, per-batch seed, next()) with the transforms on the GPU:
+    next() returns the same bytes as HostBatcher.next() for the same seed.
+
+    For each batch a host thread copies the chosen frames into a pinned arena, builds the plan
+    (esh_fixmatch_device_plan) and sends arena, plan and coefficient tables on the side stream, event-ordered
+    against the reuse of the pinned slot as HostBatcher's copies are; next() makes the caller's stream wait for
+    that event and runs one es_aug_fixmatch_u8 on it.
+    resident=True uploads the whole frame set once; a step then sends only the plan and the tables.
+    kind: 'fixmatch' -> (weak, strong), 'eval' -> (x,)."""
+
+    def __init__(self, images, batch, size, kind="fixmatch", is_crop=True, seed=0, threads=None, device="cuda",
+                 resident=False):
+        if kind not in ("fixmatch", "eval"):
+            raise ValueError("the device input path runs TransformFixMatch ('fixmatch') and its weak view ('eval')")
+        self._lib = _device()
+        self.images = [_hwc(im) for im in images]
+        self.batch, self.size, self.kind, self.is_crop = batch, size, kind, is_crop
+        self.seed, self.threads, self.device, self.resident = seed, threads, torch.device(device), resident
+        self.step = 0
+        self._ws = np.array([a.shape[1] for a in self.images], np.int32)
+        self._hs = np.array([a.shape[0] for a in self.images], np.int32)
+        nbytes = self._ws.astype(np.int64) * self._hs * 3
+        self._max_h = int(self._hs.max())
+        R = resize_side(size, is_crop)
+        ks = lambda s: int(np.ceil(max(1.0, s / R))) * 2 + 1  # noqa: E731 -- precompute()'s kernel size
+        sides = set(self._ws.tolist()) | set(self._hs.tolist())
+        coef_cap = max(1, sum(R * (2 + ks(s)) for s in sides if s != R))
+        with torch.cuda.device(self.device):
+            wbytes = self._lib.es_aug_fixmatch_workspace(batch, size, int(bool(is_crop)), int(self._ws.max()),
+                                                         self._max_h)
+            self._workspace = torch.empty(max(wbytes, 1), dtype=torch.uint8, device=self.device)
+            if resident:
+                self._offs = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
+                self._frames = torch.from_numpy(np.concatenate([a.reshape(-1) for a in self.images])).to(self.device)
+                arena_cap = 0
+            else:
+                arena_cap = batch * int(nbytes.max())
+        self._host = [{"arena": torch.empty(max(arena_cap, 1), dtype=torch.uint8, pin_memory=True),
+                       "entries": torch.empty(batch * ENTRY_BYTES, dtype=torch.uint8, pin_memory=True),
+                       "coeffs": torch.empty(coef_cap, dtype=torch.int32, pin_memory=True),
+                       "used": 0, "bytes": 0} for _ in range(2)]
+        self._stream = torch.cuda.Stream(device=self.device)
+        self._events = [None, None]
+        self._worker = None
+        self._error = None
+        self._submit(0)
+
+    def _indices(self, step):
+        g = np.random.default_rng((self.seed, step))
+        return g.integers(0, len(self.images), self.batch)
+
+    def _build(self, step):
+        try:
+            slot = step & 1
+            if self._events[slot] is not None:  # the copies out of this slot two batches ago must be done
+                self._events[slot].synchronize()
+            h = self._host[slot]
+            idx = self._indices(step)
+            h["bytes"], h["used"] = plan_and_copy(self.images, self._ws, self._hs, idx, self.size, self.is_crop,
+                                                  (self.seed << 32) ^ step, h["entries"].numpy(), h["coeffs"].numpy(),
+                                                  arena=None if self.resident else h["arena"].numpy(),
+                                                  offsets=self._offs if self.resident else None,
+                                                  threads=self.threads or 4)
+            # the copies start here, on the side stream, so they run under the step that is still computing
+            with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
+                ent = h["entries"].to(self.device, non_blocking=True)
+                coef = h["coeffs"][:max(h["used"], 1)].to(self.device, non_blocking=True)
+                frames = None if self.resident else h["arena"][:h["bytes"]].to(self.device, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(self._stream)
+            h["sent"] = (ent, coef, frames)
+            self._events[slot] = ev
+        except BaseException as e:  # surfaced by next()
+            self._error = e
+
+    def _submit(self, step):
+        self._worker = threading.Thread(target=self._build, args=(step,), daemon=True)  # ctypes drops the GIL
+        self._worker.start()
+
+    def next(self):
+        """The next batch on the device, produced on the caller's current stream (no host synchronisation)."""
+        self._worker.join()
+        if self._error is not None:
+            raise self._error
+        slot = self.step & 1
+        h = self._host[slot]
+        ent, coef, frames = h["sent"]
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(self._events[slot])
+            for d in (ent, coef, frames):
+                if d is not None:
+                    d.record_stream(cur)
+            if self.resident:
+                frames = self._frames
+            out = _run_fixmatch(frames, frames.numel(), ent, coef, h["used"], self.batch, self.size, self.is_crop,
+                                self._max_h, self.kind == "fixmatch", self._workspace, self.device)
+        h["sent"] = None
         self.step += 1
         self._submit(self.step)
         return out

@@ -193,6 +193,34 @@ int es_ln_param_grads_multi(const void* table, int n, hipStream_t stream);
 int es_gelu_fwd(const void* x, void* y, long n, hipStream_t stream);
 int es_gelu_bwd(const void* x, const void* dy, void* dx, long n, hipStream_t stream);
 
+/* ---- device input path: TransformFixMatch on the GPU (csrc/device_aug.hip) --------------------------
+ * code/dataset.py:24-56 (Resize -> [CenterCrop] = the weak view; -> RandomHorizontalFlip -> RandomCrop(S,
+ * pad int(0.125 S), reflect) -> RandAugmentMC(2, 10) = the strong view) and code/randaugment.py:147-222, from
+ * decoded RGB HWC frames of ragged sizes in one device byte arena to planar uint8 [n][3][S][S] batches (the
+ * input of the uint8 patch gather above).  Every random draw and every double-precision parameter is resolved
+ * on the host into one EsAugEntry per image plus Pillow's 22-bit bilinear tables (include/endossl_aug_plan.h;
+ * written by libendossl_host.so, include/endossl_host.h); the kernels are integer / fp32 ports of that
+ * library's pixel loops and their output is byte-identical to its batch builder's for the same (seed, index).
+ * Nothing here allocates or synchronises.
+ *
+ * The fixmatch call: frames = the arena (frames_bytes long), entries = n EsAugEntry (8-byte aligned), coeffs =
+ * coeff_count int32 of tables, max_h = the tallest frame of the batch (sizes the horizontal pass's temporary),
+ * weak / strong = the outputs; strong may be NULL (the evaluation transform, code/dataset.py:217-231).  The
+ * strong call runs the strong chain alone from S x S planar views (weak) under the entries' flip / crop / op /
+ * Cutout fields.  workspace: the byte count the matching query returns (0 for shapes the calls refuse).
+ * ES_BAD_SHAPE: n <= 0 or above 65535, S < 2 or above 4096, a reflect pad int(0.125 S) >= S, max_h <= 0;
+ * ES_BAD_ARG: a null or misaligned pointer, a workspace smaller than the query's.  An entry that points outside
+ * the arena, the tables or the temporary is skipped by the kernels (its outputs are not written). */
+size_t es_aug_entry_size(void);
+size_t es_aug_strong_workspace(int n, int S);
+size_t es_aug_fixmatch_workspace(int n, int S, int is_crop, int max_w, int max_h);
+int es_aug_fixmatch_u8(const uint8_t* frames, size_t frames_bytes, const void* entries, const int32_t* coeffs,
+                       size_t coeff_count, int n, int S, int is_crop, int max_h, uint8_t* weak, uint8_t* strong,
+                       void* workspace, size_t workspace_bytes, hipStream_t stream);
+int es_aug_strong_u8(const uint8_t* weak, const void* entries, int n, int S, uint8_t* strong, void* workspace,
+                     size_t workspace_bytes, hipStream_t stream);
+
+
 /* ---- ViT ends: patches, CLS/pos rows, embedding backward, final LN + head on CLS ------------- */
 int es_patch_im2col(const float* img, void* patches, int n, int S, int P, hipStream_t stream);
 

@@ -13,6 +13,7 @@
  * (tests/test_host_aug.py).  Status codes: 0 ok, 2 bad argument, 3 bad shape.  Thread-safe (no state). */
 #ifndef ENDOSSL_HOST_H
 #define ENDOSSL_HOST_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -59,6 +60,32 @@ int esh_pad_reflect_crop(const uint8_t* src, int w, int h, int pad, int top, int
  * is_crop: config.DATA.IS_CROP (Resize to int(1.2 S), then CenterCrop(S)); unused outputs may be NULL. */
 int esh_transform_batch(int kind, const uint8_t* const* srcs, const int* ws, const int* hs, int n, int S,
                         int is_crop, uint64_t seed, int nthreads, uint8_t* out0, uint8_t* out1, uint8_t* out2);
+
+/* ---- the plan of the device input path (include/endossl_aug_plan.h; the pixels: csrc/device_aug.hip) ---- */
+int esh_aug_entry_size(void); /* sizeof(EsAugEntry); the device library reports its own */
+
+/* The strong-chain fields of one EsAugEntry (flip, RandomCrop top / left, two RandAugmentMC slots with their
+ * parameters resolved, the Cutout rectangle) from explicit draws: ops / v / applied / neg hold two values each
+ * (pool index, magnitude 0..10, the apply draw, the sign draw), rect = x0, y0, x1, y1 as CutoutAbs hands them to
+ * ImageDraw.rectangle.  The frame and resize fields are zeroed (no tables). */
+int esh_aug_plan_from_draws(int S, int flip, int top, int left, const int* ops, const int* v, const int* applied,
+                            const int* neg, const int* rect, void* entry);
+
+/* The device path's frame arena: frames i (RGB HWC, ws[i] x hs[i]) copied back to back into arena (e.g. pinned
+ * memory) on nthreads host threads; frame_offs[i] = frame i's byte offset, *arena_used = the bytes written.
+ * Returns 3, with *arena_used = the bytes needed and nothing copied, when they exceed arena_cap. */
+int esh_copy_frames(const uint8_t* const* srcs, const int* ws, const int* hs, int n, uint8_t* arena, size_t arena_cap,
+                    int64_t* frame_offs, size_t* arena_used, int nthreads);
+
+/* The plan of esh_transform_batch(kind 0) for frames of sizes ws[i] x hs[i] and the same (seed, i): entries
+ * [n] EsAugEntry, and Pillow's 22-bit bilinear tables (one per distinct (in, out) size pair) in coeffs.
+ * frame_offs[i]: frame i's byte offset in the caller's arena (NULL: packed in order).  *coeff_used = the int32
+ * count of the tables; when it exceeds coeff_cap (or coeffs is NULL) the tables are not written and the call
+ * returns 3, so a caller can size the buffer from a first call.  The draws are esh_transform_batch's own stream
+ * in its own order: flip, top, left, both op indices, then per op magnitude, apply, sign (only when applied),
+ * then the two Cutout uniforms. */
+int esh_fixmatch_device_plan(const int* ws, const int* hs, const int64_t* frame_offs, int n, int S, int is_crop,
+                             uint64_t seed, void* entries, int32_t* coeffs, size_t coeff_cap, size_t* coeff_used);
 
 #ifdef __cplusplus
 }
