@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -29,6 +30,9 @@
 #include <vector>
 
 #include "../../include/endossl_aug_plan.h"
+
+// status codes shared with the device library (include/endossl.h)
+enum { ESH_OK = 0, ESH_BAD_ARG = 2, ESH_BAD_SHAPE = 3 };
 
 namespace {
 
@@ -886,27 +890,115 @@ bool resolve_op(EsAugOp& o, int op, int v, bool applied, bool neg, int S) {
   return true;
 }
 
-bool plan_strong(EsAugEntry& e, int S, uint64_t seed) {
-  Rng rng(seed);
-  e.flip = rng.uniform() < 0.5 ? 1 : 0;
-  const int pad = (int)(S * 0.125);
-  e.top = rng.randint(0, 2 * pad + 1);
-  e.left = rng.randint(0, 2 * pad + 1);
+// randaugment_mc(2, 10) + cutout_abs on an S x S image: the two resolved slots and the Cutout rectangle
+bool plan_randaugment(EsAugOp slots[2], int32_t rect[4], int S, Rng& rng) {
   int ops[2];
   for (int i = 0; i < 2; ++i) ops[i] = rng.randint(0, OP_COUNT);
   for (int i = 0; i < 2; ++i) {
     const int v = rng.randint(1, 10);
     const bool applied = rng.uniform() < 0.5;
     const bool neg = applied ? rng.uniform() < 0.5 : false;  // the sign draw is made only when the op runs
-    if (!resolve_op(e.ops[i], ops[i], v, applied, neg, S)) return false;
+    if (!resolve_op(slots[i], ops[i], v, applied, neg, S)) return false;
   }
   const int cv = (int)(32 * 0.5);
   const double fx = rng.uniform() * S, fy = rng.uniform() * S;
   const int x0 = (int)std::max(0.0, fx - cv / 2.0), y0 = (int)std::max(0.0, fy - cv / 2.0);
-  e.rect[0] = x0;
-  e.rect[1] = y0;
-  e.rect[2] = (int)std::min((double)S, (double)x0 + cv);
-  e.rect[3] = (int)std::min((double)S, (double)y0 + cv);
+  rect[0] = x0;
+  rect[1] = y0;
+  rect[2] = (int)std::min((double)S, (double)x0 + cv);
+  rect[3] = (int)std::min((double)S, (double)y0 + cv);
+  return true;
+}
+
+bool plan_strong(EsAugEntry& e, int S, uint64_t seed) {
+  Rng rng(seed);
+  e.flip = rng.uniform() < 0.5 ? 1 : 0;
+  const int pad = (int)(S * 0.125);
+  e.top = rng.randint(0, 2 * pad + 1);
+  e.left = rng.randint(0, 2 * pad + 1);
+  return plan_randaugment(e.ops, e.rect, S, rng);
+}
+
+// A jitter chain's device kinds from its draws: a blend at exactly 1.0 returns the image itself (as in
+// resolve_op); the hue round trip through HSV is lossy, so it runs at any shift, 0 included.
+void resolve_jitter(EsAugJitter& j) {
+  for (int k = 0; k < 4; ++k) {
+    const int o = j.order[k];
+    j.kind[k] = ES_JIT_NONE;
+    if (!j.applied || k >= j.nops) continue;
+    if (o == ES_JIT_HUE || j.factor[o] != 1.0f) j.kind[k] = o;
+  }
+}
+
+// TransformCoMatch's draws after the resize, in comatch_triplet's order (DUPLICATED from it, as plan_strong
+// duplicates fixmatch_pair; tests/test_device_aug_plans_cpu.py replays the plans against esh_transform_batch)
+bool plan_comatch(EsAugCoEntry& e, int S, uint64_t seed) {
+  Rng rng(seed);
+  e.flip_w = rng.uniform() < 0.5 ? 1 : 0;
+  e.s0.flip = rng.uniform() < 0.5 ? 1 : 0;
+  e.s0.top = e.s0.left = (int)(S * 0.125);  // no RandomCrop in this view: the window is the image itself
+  if (!plan_randaugment(e.s0.ops, e.s0.rect, S, rng)) return false;
+  EsAugJitter& j = e.jit;
+  j.nops = 4;
+  for (int k = 0; k < 4; ++k) j.order[k] = k;
+  for (int k = 0; k < 3; ++k) j.factor[k] = 1.0f;
+  j.applied = rng.uniform() < 0.8 ? 1 : 0;
+  if (j.applied) {
+    for (int i = 3; i > 0; --i) std::swap(j.order[i], j.order[rng.randint(0, i + 1)]);
+    for (int k = 0; k < 3; ++k) j.factor[k] = (float)(0.6 + 0.8 * rng.uniform());
+    const double fh = -0.1 + 0.2 * rng.uniform();
+    j.hue = (int)(fh * 255.0);  // adjust_hue's shift
+  }
+  j.gray = rng.uniform() < 0.2 ? 1 : 0;
+  j.flip = rng.uniform() < 0.5 ? 1 : 0;
+  resolve_jitter(j);
+  return true;
+}
+
+// RandomRotation's matrix on an R x R image, as rotate() / affine_nearest() resolve it
+bool resolve_rotation(EsAugLabEntry& e, double angle_deg, int R) {
+  e.angle = angle_deg;
+  e.rot = 0;
+  for (int k = 0; k < 6; ++k) e.a[k] = 0;
+  double angle = std::fmod(angle_deg, 360.0);
+  if (angle < 0) angle += 360.0;
+  if (angle == 0.0) return true;
+  if (angle == 90.0 || angle == 180.0 || angle == 270.0) return false;  // Pillow's transposes: outside (-20, 20)
+  const double cx = R / 2.0, cy = R / 2.0;
+  const double r = -(angle * (M_PI / 180.0));
+  double m[6] = {py_round15(std::cos(r)), py_round15(std::sin(r)), 0.0, py_round15(-std::sin(r)),
+                 py_round15(std::cos(r)), 0.0};
+  const double tx = m[0] * (-cx) + m[1] * (-cy) + m[2], ty = m[3] * (-cx) + m[4] * (-cy) + m[5];
+  m[2] = tx + cx;
+  m[5] = ty + cy;
+  if (m[1] == 0.0 && m[3] == 0.0)  // an angle whose sine rounds to 0: the scale path, here the identity
+    return m[0] == 1.0 && m[4] == 1.0 && m[2] == 0.0 && m[5] == 0.0;
+  auto fix = [](double q) { return (int)std::floor(q * 65536.0 + 0.5); };
+  e.rot = 1;
+  e.a[0] = fix(m[0]);
+  e.a[1] = fix(m[1]);
+  e.a[3] = fix(m[3]);
+  e.a[4] = fix(m[4]);
+  e.a[2] = fix(m[2] + m[1] * 0.5 + m[0] * 0.5);
+  e.a[5] = fix(m[5] + m[4] * 0.5 + m[3] * 0.5);
+  return true;
+}
+
+// labeled_train's draws after the resize, in its order (DUPLICATED from it; same guard)
+bool plan_labeled(EsAugLabEntry& e, int R, uint64_t seed) {
+  Rng rng(seed);
+  e.hflip = rng.uniform() < 0.3 ? 1 : 0;
+  e.vflip = rng.uniform() < 0.3 ? 1 : 0;
+  if (!resolve_rotation(e, -20.0 + 40.0 * rng.uniform(), R)) return false;
+  EsAugJitter& j = e.jit;
+  j.applied = 1;
+  j.nops = 3;
+  j.order[3] = ES_JIT_HUE;  // unused: past nops
+  for (int k = 0; k < 3; ++k) j.order[k] = k;
+  for (int i = 2; i > 0; --i) std::swap(j.order[i], j.order[rng.randint(0, i + 1)]);
+  // one factor is drawn per POSITION, for whichever op stands there
+  for (int k = 0; k < 3; ++k) j.factor[j.order[k]] = (float)(0.8 + 0.4 * rng.uniform());
+  resolve_jitter(j);
   return true;
 }
 
@@ -932,14 +1024,77 @@ void parallel_for(int n, int nthreads, F f) {
   for (auto& t : ts) t.join();
 }
 
+// The frame / resize head of every entry (any entry type begins with EsAugHead's fields) and the shared
+// coefficient tables; fill(entry, i) then writes the transform's own draws.  The contract of every
+// esh_*_device_plan: see esh_fixmatch_device_plan.
+template <class Entry, class Fill>
+int device_plan(const int* ws, const int* hs, const int64_t* frame_offs, int n, int S, int is_crop, void* entries,
+                int32_t* coeffs, size_t coeff_cap, size_t* coeff_used, Fill fill) {
+  if (!ws || !hs || n <= 0 || !entries || !coeff_used) return ESH_BAD_ARG;
+  if (S < 2) return ESH_BAD_SHAPE;
+  const int R = is_crop ? (int)(S * 1.2) : S;
+  if (R < S || (int)(S * 0.125) >= S) return ESH_BAD_SHAPE;
+  for (int i = 0; i < n; ++i)
+    if (ws[i] <= 0 || hs[i] <= 0 || (frame_offs && frame_offs[i] < 0)) return ESH_BAD_SHAPE;
+  std::vector<PlanTable> tabs;
+  size_t used = 0;
+  auto table = [&](int in) -> const PlanTable& {
+    for (const PlanTable& t : tabs)
+      if (t.in == in) return t;
+    const double scale = (double)in / R;
+    const int ksize = (int)std::ceil(scale < 1.0 ? 1.0 : scale) * 2 + 1;  // precompute()'s
+    tabs.push_back(PlanTable{in, R, ksize, used});
+    used += (size_t)R * 2 + (size_t)R * ksize;
+    return tabs.back();
+  };
+  Entry* es = (Entry*)entries;
+  const int crop = is_crop ? py_round_half_even((R - S) / 2.0) : 0;
+  int64_t packed = 0;
+  for (int i = 0; i < n; ++i) {
+    Entry e;
+    std::memset(&e, 0, sizeof e);
+    EsAugHead h;
+    std::memset(&h, 0, sizeof h);
+    h.frame_off = frame_offs ? frame_offs[i] : packed;
+    packed += (int64_t)ws[i] * hs[i] * 3;
+    h.w = ws[i];
+    h.h = hs[i];
+    h.coef_h = h.coef_v = -1;
+    if (h.w != R) {
+      const PlanTable& t = table(h.w);
+      h.coef_h = (int32_t)t.off;
+      h.ksize_h = t.ksize;
+    }
+    if (h.h != R) {
+      const PlanTable& t = table(h.h);
+      h.coef_v = (int32_t)t.off;
+      h.ksize_v = t.ksize;
+    }
+    h.crop = crop;
+    std::memcpy(&e, &h, offsetof(EsAugHead, crop) + sizeof h.crop);
+    if (!fill(e, i)) return ESH_BAD_ARG;
+    std::memcpy(&es[i], &e, sizeof e);
+  }
+  *coeff_used = used;
+  if (used > (size_t)INT32_MAX) return ESH_BAD_SHAPE;  // the entries hold 32-bit table offsets
+  if (!coeffs || used > coeff_cap) return ESH_BAD_SHAPE;
+  for (const PlanTable& t : tabs) {
+    const Coeffs c = precompute(t.in, t.out);
+    int32_t* dst = coeffs + t.off;
+    for (size_t k = 0; k < c.bounds.size(); ++k) dst[k] = c.bounds[k];
+    for (size_t k = 0; k < c.kk.size(); ++k) dst[c.bounds.size() + k] = c.kk[k];
+  }
+  return ESH_OK;
+}
+
+static_assert(offsetof(EsAugEntry, flip) == offsetof(EsAugHead, crop) + sizeof(int32_t), "EsAugEntry begins with the head");
+static_assert(offsetof(EsAugEntry, flip) + sizeof(EsAugStrong) == sizeof(EsAugEntry), "EsAugStrong is EsAugEntry's tail");
+
 bool bad_img(const u8* p, int w, int h) { return !p || w <= 0 || h <= 0; }
 
 }  // namespace
 
 extern "C" {
-
-// status codes shared with the device library (include/endossl.h)
-enum { ESH_OK = 0, ESH_BAD_ARG = 2, ESH_BAD_SHAPE = 3 };
 
 int esh_abi_version(void) { return 2; }
 
@@ -1098,57 +1253,73 @@ int esh_copy_frames(const uint8_t* const* srcs, const int* ws, const int* hs, in
 // and the call returns ESH_BAD_SHAPE, so a caller can size the buffer and call again.
 int esh_fixmatch_device_plan(const int* ws, const int* hs, const int64_t* frame_offs, int n, int S, int is_crop,
                              uint64_t seed, void* entries, int32_t* coeffs, size_t coeff_cap, size_t* coeff_used) {
-  if (!ws || !hs || n <= 0 || !entries || !coeff_used) return ESH_BAD_ARG;
+  return device_plan<EsAugEntry>(ws, hs, frame_offs, n, S, is_crop, entries, coeffs, coeff_cap, coeff_used,
+                                 [&](EsAugEntry& e, int i) { return plan_strong(e, S, image_seed(seed, (uint64_t)i, 0)); });
+}
+
+// The same for esh_transform_batch(kind 2), TransformCoMatch: entries [n] EsAugCoEntry
+int esh_comatch_entry_size(void) { return (int)sizeof(EsAugCoEntry); }
+
+int esh_comatch_device_plan(const int* ws, const int* hs, const int64_t* frame_offs, int n, int S, int is_crop,
+                            uint64_t seed, void* entries, int32_t* coeffs, size_t coeff_cap, size_t* coeff_used) {
+  return device_plan<EsAugCoEntry>(ws, hs, frame_offs, n, S, is_crop, entries, coeffs, coeff_cap, coeff_used,
+                                   [&](EsAugCoEntry& e, int i) { return plan_comatch(e, S, image_seed(seed, (uint64_t)i, 2)); });
+}
+
+// ... and for esh_transform_batch(kind 1), the labeled train transform: entries [n] EsAugLabEntry
+int esh_labeled_entry_size(void) { return (int)sizeof(EsAugLabEntry); }
+
+int esh_labeled_device_plan(const int* ws, const int* hs, const int64_t* frame_offs, int n, int S, int is_crop,
+                            uint64_t seed, void* entries, int32_t* coeffs, size_t coeff_cap, size_t* coeff_used) {
+  const int R = is_crop ? (int)(S * 1.2) : S;
+  return device_plan<EsAugLabEntry>(ws, hs, frame_offs, n, S, is_crop, entries, coeffs, coeff_cap, coeff_used,
+                                    [&](EsAugLabEntry& e, int i) { return plan_labeled(e, R, image_seed(seed, (uint64_t)i, 1)); });
+}
+
+// One EsAugJitter from explicit draws: order holds nops (3 or 4) distinct ES_JIT_* values (hue only with 4),
+// factors = brightness, contrast, saturation, hue_factor in [-0.5, 0.5] (adjust_hue's argument).
+int esh_jitter_plan_from_draws(int applied, int nops, const int* order, const float* factors, double hue_factor,
+                               int gray, int flip, void* jitter) {
+  if (!order || !factors || !jitter || (nops != 3 && nops != 4)) return ESH_BAD_ARG;
+  if (!(hue_factor >= -0.5 && hue_factor <= 0.5)) return ESH_BAD_ARG;
+  int seen = 0;
+  for (int k = 0; k < nops; ++k) {
+    if (order[k] < 0 || order[k] >= nops || (seen >> order[k] & 1)) return ESH_BAD_ARG;
+    seen |= 1 << order[k];
+  }
+  EsAugJitter j;
+  std::memset(&j, 0, sizeof j);
+  j.applied = applied != 0;
+  j.nops = nops;
+  j.order[3] = ES_JIT_HUE;
+  for (int k = 0; k < nops; ++k) j.order[k] = order[k];
+  for (int k = 0; k < 3; ++k) j.factor[k] = factors[k];
+  j.hue = (int)(hue_factor * 255.0);
+  j.gray = gray != 0;
+  j.flip = flip != 0;
+  resolve_jitter(j);
+  std::memcpy(jitter, &j, sizeof j);
+  return ESH_OK;
+}
+
+// The transform fields of one EsAugLabEntry (flips, the rotation on the R x R image, a three-op jitter chain)
+// from explicit draws; the frame and resize fields of *entry are zeroed (no tables) except crop.
+int esh_labeled_plan_from_draws(int S, int is_crop, int hflip, int vflip, double angle_deg, const int* order,
+                                const float* factors, void* entry) {
+  if (!order || !factors || !entry || !(angle_deg == angle_deg)) return ESH_BAD_ARG;
   if (S < 2) return ESH_BAD_SHAPE;
   const int R = is_crop ? (int)(S * 1.2) : S;
-  if (R < S || (int)(S * 0.125) >= S) return ESH_BAD_SHAPE;
-  for (int i = 0; i < n; ++i)
-    if (ws[i] <= 0 || hs[i] <= 0 || (frame_offs && frame_offs[i] < 0)) return ESH_BAD_SHAPE;
-  std::vector<PlanTable> tabs;
-  size_t used = 0;
-  auto table = [&](int in) -> const PlanTable& {
-    for (const PlanTable& t : tabs)
-      if (t.in == in) return t;
-    const double scale = (double)in / R;
-    const int ksize = (int)std::ceil(scale < 1.0 ? 1.0 : scale) * 2 + 1;  // precompute()'s
-    tabs.push_back(PlanTable{in, R, ksize, used});
-    used += (size_t)R * 2 + (size_t)R * ksize;
-    return tabs.back();
-  };
-  EsAugEntry* es = (EsAugEntry*)entries;
-  const int crop = is_crop ? py_round_half_even((R - S) / 2.0) : 0;
-  int64_t packed = 0;
-  for (int i = 0; i < n; ++i) {
-    EsAugEntry e;
-    std::memset(&e, 0, sizeof e);
-    e.frame_off = frame_offs ? frame_offs[i] : packed;
-    packed += (int64_t)ws[i] * hs[i] * 3;
-    e.w = ws[i];
-    e.h = hs[i];
-    e.coef_h = e.coef_v = -1;
-    if (e.w != R) {
-      const PlanTable& t = table(e.w);
-      e.coef_h = (int32_t)t.off;
-      e.ksize_h = t.ksize;
-    }
-    if (e.h != R) {
-      const PlanTable& t = table(e.h);
-      e.coef_v = (int32_t)t.off;
-      e.ksize_v = t.ksize;
-    }
-    e.crop = crop;
-    if (!plan_strong(e, S, image_seed(seed, (uint64_t)i, 0))) return ESH_BAD_ARG;
-    std::memcpy(&es[i], &e, sizeof e);
-  }
-  *coeff_used = used;
-  if (used > (size_t)INT32_MAX) return ESH_BAD_SHAPE;  // the entries hold 32-bit table offsets
-  if (!coeffs || used > coeff_cap) return ESH_BAD_SHAPE;
-  for (const PlanTable& t : tabs) {
-    const Coeffs c = precompute(t.in, t.out);
-    int32_t* dst = coeffs + t.off;
-    for (size_t k = 0; k < c.bounds.size(); ++k) dst[k] = c.bounds[k];
-    for (size_t k = 0; k < c.kk.size(); ++k) dst[c.bounds.size() + k] = c.kk[k];
-  }
+  if (R < S) return ESH_BAD_SHAPE;
+  EsAugLabEntry e;
+  std::memset(&e, 0, sizeof e);
+  e.head.coef_h = e.head.coef_v = -1;
+  e.head.crop = is_crop ? py_round_half_even((R - S) / 2.0) : 0;
+  e.hflip = hflip != 0;
+  e.vflip = vflip != 0;
+  if (!resolve_rotation(e, angle_deg, R)) return ESH_BAD_ARG;
+  const int rc = esh_jitter_plan_from_draws(1, 3, order, factors, 0.0, 0, 0, &e.jit);
+  if (rc != ESH_OK) return rc;
+  std::memcpy(entry, &e, sizeof e);
   return ESH_OK;
 }
 

@@ -196,6 +196,13 @@ SIGNATURES = {
     "es_aug_fixmatch_workspace": (Z, [I, I, I, I, I]),
     "es_aug_fixmatch_u8": (I, [V, Z, V, V, Z, I, I, I, I, V, V, V, Z, V]),
     "es_aug_strong_u8": (I, [V, V, I, I, V, V, Z, V]),
+    "es_aug_comatch_entry_size": (Z, []),
+    "es_aug_labeled_entry_size": (Z, []),
+    "es_aug_comatch_workspace": (Z, [I, I, I, I, I]),
+    "es_aug_labeled_workspace": (Z, [I, I, I, I, I]),
+    "es_aug_comatch_u8": (I, [V, Z, V, V, Z, I, I, I, I, V, V, V, V, Z, V]),
+    "es_aug_labeled_u8": (I, [V, Z, V, V, Z, I, I, I, I, V, V, Z, V]),
+    "es_aug_jitter_u8": (I, [V, V, I, I, V, V]),
 }
 
 ABI_VERSION = 1

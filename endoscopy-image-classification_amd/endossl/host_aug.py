@@ -51,6 +51,16 @@ _SIG = {
     "esh_copy_frames": (_I, [_P, _P, _P, _I, _P, ctypes.c_size_t, _P, ctypes.POINTER(ctypes.c_size_t), _I]),
     "esh_fixmatch_device_plan": (_I, [_P, _P, _P, _I, _I, _I, ctypes.c_uint64, _P, _P, ctypes.c_size_t,
                                       ctypes.POINTER(ctypes.c_size_t)]),
+    "esh_comatch_entry_size": (_I, []),
+    "esh_labeled_entry_size": (_I, []),
+    "esh_comatch_device_plan": (_I, [_P, _P, _P, _I, _I, _I, ctypes.c_uint64, _P, _P, ctypes.c_size_t,
+                                     ctypes.POINTER(ctypes.c_size_t)]),
+    "esh_labeled_device_plan": (_I, [_P, _P, _P, _I, _I, _I, ctypes.c_uint64, _P, _P, ctypes.c_size_t,
+                                     ctypes.POINTER(ctypes.c_size_t)]),
+    "esh_jitter_plan_from_draws": (_I, [_I, _I, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_float), ctypes.c_double,
+                                        _I, _I, _P]),
+    "esh_labeled_plan_from_draws": (_I, [_I, _I, _I, _I, ctypes.c_double, ctypes.POINTER(_I),
+                                         ctypes.POINTER(ctypes.c_float), _P]),
 }
 
 
@@ -70,8 +80,47 @@ class AugEntry(ctypes.Structure):
                 ("top", ctypes.c_int32), ("left", ctypes.c_int32), ("ops", AugOp * 2), ("rect", ctypes.c_int32 * 4)]
 
 
+class AugHead(ctypes.Structure):
+    """EsAugHead: the frame / resize fields every entry begins with."""
+    _fields_ = [("frame_off", ctypes.c_int64), ("w", ctypes.c_int32), ("h", ctypes.c_int32),
+                ("coef_h", ctypes.c_int32), ("ksize_h", ctypes.c_int32), ("coef_v", ctypes.c_int32),
+                ("ksize_v", ctypes.c_int32), ("crop", ctypes.c_int32)]
+
+
+class AugStrong(ctypes.Structure):
+    """EsAugStrong: the strong chain's fields (AugEntry's from `flip` on)."""
+    _fields_ = [("flip", ctypes.c_int32), ("top", ctypes.c_int32), ("left", ctypes.c_int32), ("ops", AugOp * 2),
+                ("rect", ctypes.c_int32 * 4)]
+
+
+class AugJitter(ctypes.Structure):
+    """EsAugJitter: a ColorJitter chain, RandomGrayscale and the flip; order / kind hold JITTER indices."""
+    _fields_ = [("applied", ctypes.c_int32), ("nops", ctypes.c_int32), ("order", ctypes.c_int32 * 4),
+                ("factor", ctypes.c_float * 3), ("hue", ctypes.c_int32), ("gray", ctypes.c_int32),
+                ("flip", ctypes.c_int32), ("kind", ctypes.c_int32 * 4)]
+
+
+class CoEntry(ctypes.Structure):
+    """EsAugCoEntry: one image's TransformCoMatch plan."""
+    _fields_ = [("head", AugHead), ("flip_w", ctypes.c_int32), ("s0", AugStrong), ("jit", AugJitter)]
+
+
+class LabEntry(ctypes.Structure):
+    """EsAugLabEntry: one image's labeled-transform plan."""
+    _fields_ = [("head", AugHead), ("hflip", ctypes.c_int32), ("vflip", ctypes.c_int32), ("rot", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("angle", ctypes.c_double), ("a", ctypes.c_int32 * 6),
+                ("jit", AugJitter)]
+
+
 ENTRY_BYTES = ctypes.sizeof(AugEntry)
 AUG_NONE, AUG_SHIFT = 5, 14  # EsAugOp.kind beside the pool indices
+JITTER = ("brightness", "contrast", "saturation", "hue")  # EsAugJitter.order / kind; 4 = none
+JIT_NONE = 4
+# the device path's kinds: entry type, the two libraries' size queries, the host plan function
+_PLANS = {"fixmatch": (AugEntry, "esh_aug_entry_size", "es_aug_entry_size", "esh_fixmatch_device_plan"),
+          "eval": (AugEntry, "esh_aug_entry_size", "es_aug_entry_size", "esh_fixmatch_device_plan"),
+          "comatch": (CoEntry, "esh_comatch_entry_size", "es_aug_comatch_entry_size", "esh_comatch_device_plan"),
+          "labeled": (LabEntry, "esh_labeled_entry_size", "es_aug_labeled_entry_size", "esh_labeled_device_plan")}
 _lib = None
 _lock = threading.Lock()
 
@@ -93,9 +142,10 @@ def load():
                 fn.restype, fn.argtypes = res, args
             if lib.esh_abi_version() != ABI_VERSION:
                 raise HostLibraryError(f"host ABI {lib.esh_abi_version()} != {ABI_VERSION}")
-            if lib.esh_aug_entry_size() != ENTRY_BYTES:
-                raise HostLibraryError(f"EsAugEntry is {lib.esh_aug_entry_size()} bytes in the host library, "
-                                       f"{ENTRY_BYTES} in host_aug.AugEntry")
+            for cls, query, _, _ in _PLANS.values():
+                if getattr(lib, query)() != ctypes.sizeof(cls):
+                    raise HostLibraryError(f"{query}() is {getattr(lib, query)()} bytes in the host library, "
+                                           f"host_aug.{cls.__name__} is {ctypes.sizeof(cls)}")
             _lib = lib
     return _lib
 
@@ -300,15 +350,16 @@ _dev = None
 
 
 def _device():
-    """libendossl_hip.so, once its EsAugEntry is known to be the host library's and this module's."""
+    """libendossl_hip.so, once its three plan entries are known to be the host library's and this module's."""
     global _dev
     if _dev is None:
         from . import _lib
         lib = _lib.load()
         load()
-        if lib.es_aug_entry_size() != ENTRY_BYTES:
-            raise HostLibraryError(f"EsAugEntry is {lib.es_aug_entry_size()} bytes in the device library, "
-                                   f"{ENTRY_BYTES} in the host library")
+        for cls, _, query, _ in _PLANS.values():
+            if getattr(lib, query)() != ctypes.sizeof(cls):
+                raise HostLibraryError(f"{query}() is {getattr(lib, query)()} bytes in the device library, "
+                                       f"{ctypes.sizeof(cls)} in the host library")
         _dev = lib
     return _dev
 
@@ -329,6 +380,30 @@ def aug_plan_from_draws(size, flip, top, left, ops, v, applied, neg, rect):
     return e
 
 
+def jitter_plan_from_draws(order, factors=(1.0, 1.0, 1.0), hue=0.0, gray=False, flip=False, applied=True):
+    """One AugJitter from explicit draws: order = 3 or 4 ops (JITTER names or indices; 'hue' only among 4),
+    factors = brightness, contrast, saturation, hue = adjust_hue's factor in [-0.5, 0.5]."""
+    order = [JITTER.index(o) if isinstance(o, str) else int(o) for o in order]
+    j = AugJitter()
+    _check(load().esh_jitter_plan_from_draws(int(bool(applied)), len(order), (_I * len(order))(*order),
+                                             (ctypes.c_float * 3)(*[float(f) for f in factors]), float(hue),
+                                             int(bool(gray)), int(bool(flip)), ctypes.addressof(j)),
+           "esh_jitter_plan_from_draws")
+    return j
+
+
+def labeled_plan_from_draws(size, is_crop, hflip, vflip, angle, order=(0, 1, 2), factors=(1.0, 1.0, 1.0)):
+    """One LabEntry's transform fields from explicit draws (angle in degrees; order / factors as above, three
+    ops); its frame and resize fields are empty: device_transform_batch(plans=...) fills them."""
+    order = [JITTER.index(o) if isinstance(o, str) else int(o) for o in order]
+    e = LabEntry()
+    _check(load().esh_labeled_plan_from_draws(int(size), int(bool(is_crop)), int(bool(hflip)), int(bool(vflip)),
+                                              float(angle), (_I * len(order))(*order),
+                                              (ctypes.c_float * 3)(*[float(f) for f in factors]), ctypes.addressof(e)),
+           "esh_labeled_plan_from_draws")
+    return e
+
+
 def fixmatch_device_plan(ws, hs, size, is_crop=True, seed=0, frame_offs=None, entries=None, coeffs=None):
     """The plan of transform_batch(kind='fixmatch') for frames of sizes ws x hs and the same (seed, index).
 
@@ -336,32 +411,50 @@ def fixmatch_device_plan(ws, hs, size, is_crop=True, seed=0, frame_offs=None, en
     plan_entries()), coeffs an int32 array whose first `used` values are the resize tables.  `entries` /
     `coeffs` may be preallocated (e.g. numpy views of pinned tensors); a coeffs buffer that is too small is
     replaced by a fresh array.  frame_offs: each frame's byte offset in the arena (default: packed in order)."""
+    return device_plan("fixmatch", ws, hs, size, is_crop, seed, frame_offs, entries, coeffs)
+
+
+def comatch_device_plan(ws, hs, size, is_crop=True, seed=0, frame_offs=None, entries=None, coeffs=None):
+    """The plan of transform_batch(kind='comatch'): fixmatch_device_plan's contract with CoEntry entries
+    (plan_entries(entries, 'comatch'))."""
+    return device_plan("comatch", ws, hs, size, is_crop, seed, frame_offs, entries, coeffs)
+
+
+def labeled_device_plan(ws, hs, size, is_crop=True, seed=0, frame_offs=None, entries=None, coeffs=None):
+    """The plan of transform_batch(kind='labeled'): fixmatch_device_plan's contract with LabEntry entries
+    (plan_entries(entries, 'labeled'))."""
+    return device_plan("labeled", ws, hs, size, is_crop, seed, frame_offs, entries, coeffs)
+
+
+def device_plan(kind, ws, hs, size, is_crop=True, seed=0, frame_offs=None, entries=None, coeffs=None):
+    """The plan of transform_batch(kind) ('eval' shares 'fixmatch's): see fixmatch_device_plan."""
+    cls, _, _, fn = _PLANS[kind]
     ws = np.ascontiguousarray(ws, np.int32)
     hs = np.ascontiguousarray(hs, np.int32)
     n = len(ws)
     if entries is None:
-        entries = np.zeros((n, ENTRY_BYTES), np.uint8)
+        entries = np.zeros((n, ctypes.sizeof(cls)), np.uint8)
     if coeffs is None:
         coeffs = np.zeros(4096, np.int32)
     offs = None if frame_offs is None else np.ascontiguousarray(frame_offs, np.int64)
     used = ctypes.c_size_t()
-    lib = load()
+    plan = getattr(load(), fn)
     for _ in range(2):
-        rc = lib.esh_fixmatch_device_plan(_ptr(ws), _ptr(hs), None if offs is None else _ptr(offs), n, int(size),
-                                          int(bool(is_crop)), int(seed) & (2 ** 64 - 1), _ptr(entries), _ptr(coeffs),
-                                          coeffs.size, ctypes.byref(used))
+        rc = plan(_ptr(ws), _ptr(hs), None if offs is None else _ptr(offs), n, int(size), int(bool(is_crop)),
+                  int(seed) & (2 ** 64 - 1), _ptr(entries), _ptr(coeffs), coeffs.size, ctypes.byref(used))
         if rc == 3 and used.value > coeffs.size:  # sized by the refused call
             coeffs = np.zeros(used.value, np.int32)
             continue
         break
-    _check(rc, "esh_fixmatch_device_plan")
+    _check(rc, fn)
     return entries, coeffs, used.value
 
 
-def plan_entries(entries):
-    """A uint8 plan buffer as a ctypes array of AugEntry (sharing its memory)."""
-    n = entries.size // ENTRY_BYTES
-    return (AugEntry * n).from_buffer(entries)
+def plan_entries(entries, kind="fixmatch"):
+    """A uint8 plan buffer as a ctypes array of the kind's entry type (sharing its memory)."""
+    cls = _PLANS[kind][0]
+    n = entries.size // ctypes.sizeof(cls)
+    return (cls * n).from_buffer(entries)
 
 
 def _dev_u8(a, device):
@@ -388,40 +481,74 @@ def device_strong(weak, entries, workspace=None):
     return strong
 
 
-def _run_fixmatch(frames, frames_bytes, ent, coef, used, n, size, is_crop, max_h, want_strong, workspace, device):
-    """One es_aug_fixmatch_u8 call on the current stream over device buffers; returns the views."""
+def device_jitter(x, plans):
+    """One jitter chain (the ColorJitter ops in each plan's order, grayscale, flip) over a device uint8
+    [n, 3, S, S] batch under explicit plans (a list of AugJitter): es_aug_jitter_u8."""
     from . import _lib
-    weak = torch.empty((n, 3, size, size), dtype=torch.uint8, device=device)
-    strong = torch.empty_like(weak) if want_strong else None
-    _lib.call("es_aug_fixmatch_u8", _lib.ptr(frames), frames_bytes, _lib.ptr(ent), _lib.ptr(coef) if used else None,
-              used, n, size, int(bool(is_crop)), max_h, _lib.ptr(weak), _lib.ptr(strong), _lib.ptr(workspace),
-              workspace.numel(), _lib.stream())
-    return (weak, strong) if want_strong else (weak,)
+    _device()
+    n, _, S, _ = x.shape
+    if len(plans) != n:
+        raise ValueError("one plan per image")
+    ent = _dev_u8(np.frombuffer(bytearray(b"".join(bytes(j) for j in plans)), np.uint8), x.device)
+    out = torch.empty_like(x, memory_format=torch.contiguous_format)
+    _lib.call("es_aug_jitter_u8", _lib.ptr(x.contiguous()), _lib.ptr(ent), n, S, _lib.ptr(out), _lib.stream())
+    return out
 
 
-def device_transform_batch(images, size, kind="fixmatch", is_crop=True, seed=0, device="cuda"):
-    """transform_batch(kind='fixmatch' | 'eval') with the pixels made on the GPU: the frames are copied to the
-    device as they are, the host only builds the plan.  Returns device uint8 [n, 3, S, S] tensors, byte for
-    byte transform_batch's for the same seed."""
-    if kind not in ("fixmatch", "eval"):
-        raise ValueError("the device input path runs TransformFixMatch ('fixmatch') and its weak view ('eval')")
+# the device calls by kind: (entry point, workspace query, views)
+_CALLS = {"fixmatch": ("es_aug_fixmatch_u8", "es_aug_fixmatch_workspace", 2),
+          "eval": ("es_aug_fixmatch_u8", "es_aug_fixmatch_workspace", 1),
+          "comatch": ("es_aug_comatch_u8", "es_aug_comatch_workspace", 3),
+          "labeled": ("es_aug_labeled_u8", "es_aug_labeled_workspace", 1)}
+
+
+def _check_kind(kind):
+    if kind not in _CALLS:
+        raise ValueError(f"the device input path runs {sorted(_CALLS)}, not {kind!r}")
+
+
+def _run_device(kind, frames, frames_bytes, ent, coef, used, n, size, is_crop, max_h, workspace, device):
+    """The kind's es_aug_*_u8 call on the current stream over device buffers; returns the views."""
+    from . import _lib
+    fn, _, nout = _CALLS[kind]
+    outs = [torch.empty((n, 3, size, size), dtype=torch.uint8, device=device) for _ in range(nout)]
+    views = [_lib.ptr(t) for t in outs] + ([None] if kind == "eval" else [])  # eval: fixmatch without a strong view
+    _lib.call(fn, _lib.ptr(frames), frames_bytes, _lib.ptr(ent), _lib.ptr(coef) if used else None, used, n, size,
+              int(bool(is_crop)), max_h, *views, _lib.ptr(workspace), workspace.numel(), _lib.stream())
+    return tuple(outs)
+
+
+def device_transform_batch(images, size, kind="fixmatch", is_crop=True, seed=0, device="cuda", plans=None):
+    """transform_batch(kind='fixmatch' | 'eval' | 'comatch' | 'labeled') with the pixels made on the GPU: the
+    frames are copied to the device as they are, the host only builds the plan.  Returns device uint8
+    [n, 3, S, S] tensors, byte for byte transform_batch's for the same seed.
+    plans: one explicit entry per image (e.g. labeled_plan_from_draws) whose transform fields replace the seeded
+    draws; the frame and resize fields stay the plan's own."""
+    _check_kind(kind)
     lib = _device()
     arrs = [_hwc(im) for im in images]
     n = len(arrs)
     ws = [a.shape[1] for a in arrs]
     hs = [a.shape[0] for a in arrs]
-    entries, coeffs, used = fixmatch_device_plan(ws, hs, size, is_crop, seed)
+    entries, coeffs, used = device_plan(kind, ws, hs, size, is_crop, seed)
+    if plans is not None:
+        if len(plans) != n:
+            raise ValueError("one plan per image")
+        skip = AugHead.crop.offset + 4
+        for i, e in enumerate(plans):
+            entries[i, skip:] = np.frombuffer(bytes(e), np.uint8)[skip:]
     arena = np.concatenate([a.reshape(-1) for a in arrs])
     dev = torch.device(device)
     with torch.cuda.device(dev):
-        nbytes = lib.es_aug_fixmatch_workspace(n, size, int(bool(is_crop)), max(ws), max(hs))
+        nbytes = getattr(lib, _CALLS[kind][1])(n, size, int(bool(is_crop)), max(ws), max(hs))
         workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         coef = torch.from_numpy(coeffs[:max(used, 1)]).to(dev)
-        return _run_fixmatch(torch.from_numpy(arena).to(dev), arena.size, _dev_u8(entries, dev), coef, used, n, size,
-                             is_crop, max(hs), kind == "fixmatch", workspace, dev)
+        return _run_device(kind, torch.from_numpy(arena).to(dev), arena.size, _dev_u8(entries, dev), coef, used, n,
+                           size, is_crop, max(hs), workspace, dev)
 
 
-def plan_and_copy(images, ws, hs, idx, size, is_crop, seed, entries, coeffs, arena=None, offsets=None, threads=1):
+def plan_and_copy(images, ws, hs, idx, size, is_crop, seed, entries, coeffs, arena=None, offsets=None, threads=1,
+                  kind="fixmatch"):
     """The host's whole share of one device-path batch: frames images[idx] copied back to back into `arena` on
     `threads` host threads (or, with the frame set already on the device, `offsets` = every frame's offset
     there) and the plan written into `entries` / `coeffs` (numpy views, e.g. of pinned tensors).  Returns
@@ -436,8 +563,7 @@ def plan_and_copy(images, ws, hs, idx, size, is_crop, seed, entries, coeffs, are
         _check(load().esh_copy_frames(_ptr(ptrs), _ptr(ws), _ptr(hs), len(idx), _ptr(arena), arena.size, _ptr(offs),
                                       ctypes.byref(used), int(threads)), "esh_copy_frames")
         pos = used.value
-    _, out, used = fixmatch_device_plan(ws, hs, size, is_crop, seed=seed, frame_offs=offs, entries=entries,
-                                        coeffs=coeffs)
+    _, out, used = device_plan(kind, ws, hs, size, is_crop, seed=seed, frame_offs=offs, entries=entries, coeffs=coeffs)
     if out is not coeffs:
         raise ValueError(f"coefficient buffer of {coeffs.size} int32 is too small: {used} needed")
     return pos, used
@@ -448,16 +574,15 @@ class DeviceBatcher:
     next() returns the same bytes as HostBatcher.next() for the same seed.
 
     For each batch a host thread copies the chosen frames into a pinned arena, builds the plan
-    (esh_fixmatch_device_plan) and sends arena, plan and coefficient tables on the side stream, event-ordered
+    (esh_*_device_plan) and sends arena, plan and coefficient tables on the side stream, event-ordered
     against the reuse of the pinned slot as HostBatcher's copies are; next() makes the caller's stream wait for
-    that event and runs one es_aug_fixmatch_u8 on it.
+    that event and runs the kind's one es_aug_*_u8 call on it.
     resident=True uploads the whole frame set once; a step then sends only the plan and the tables.
-    kind: 'fixmatch' -> (weak, strong), 'eval' -> (x,)."""
+    kind: 'fixmatch' -> (weak, strong), 'comatch' -> (weak, strong_0, strong_1), 'labeled' / 'eval' -> (x,)."""
 
     def __init__(self, images, batch, size, kind="fixmatch", is_crop=True, seed=0, threads=None, device="cuda",
                  resident=False):
-        if kind not in ("fixmatch", "eval"):
-            raise ValueError("the device input path runs TransformFixMatch ('fixmatch') and its weak view ('eval')")
+        _check_kind(kind)
         self._lib = _device()
         self.images = [_hwc(im) for im in images]
         self.batch, self.size, self.kind, self.is_crop = batch, size, kind, is_crop
@@ -472,7 +597,7 @@ class DeviceBatcher:
         sides = set(self._ws.tolist()) | set(self._hs.tolist())
         coef_cap = max(1, sum(R * (2 + ks(s)) for s in sides if s != R))
         with torch.cuda.device(self.device):
-            wbytes = self._lib.es_aug_fixmatch_workspace(batch, size, int(bool(is_crop)), int(self._ws.max()),
+            wbytes = getattr(self._lib, _CALLS[kind][1])(batch, size, int(bool(is_crop)), int(self._ws.max()),
                                                          self._max_h)
             self._workspace = torch.empty(max(wbytes, 1), dtype=torch.uint8, device=self.device)
             if resident:
@@ -482,7 +607,8 @@ class DeviceBatcher:
             else:
                 arena_cap = batch * int(nbytes.max())
         self._host = [{"arena": torch.empty(max(arena_cap, 1), dtype=torch.uint8, pin_memory=True),
-                       "entries": torch.empty(batch * ENTRY_BYTES, dtype=torch.uint8, pin_memory=True),
+                       "entries": torch.empty(batch * ctypes.sizeof(_PLANS[kind][0]), dtype=torch.uint8,
+                                              pin_memory=True),
                        "coeffs": torch.empty(coef_cap, dtype=torch.int32, pin_memory=True),
                        "used": 0, "bytes": 0} for _ in range(2)]
         self._stream = torch.cuda.Stream(device=self.device)
@@ -506,7 +632,7 @@ class DeviceBatcher:
                                                   (self.seed << 32) ^ step, h["entries"].numpy(), h["coeffs"].numpy(),
                                                   arena=None if self.resident else h["arena"].numpy(),
                                                   offsets=self._offs if self.resident else None,
-                                                  threads=self.threads or 4)
+                                                  threads=self.threads or 4, kind=self.kind)
             # the copies start here, on the side stream, so they run under the step that is still computing
             with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
                 ent = h["entries"].to(self.device, non_blocking=True)
@@ -539,8 +665,8 @@ class DeviceBatcher:
                     d.record_stream(cur)
             if self.resident:
                 frames = self._frames
-            out = _run_fixmatch(frames, frames.numel(), ent, coef, h["used"], self.batch, self.size, self.is_crop,
-                                self._max_h, self.kind == "fixmatch", self._workspace, self.device)
+            out = _run_device(self.kind, frames, frames.numel(), ent, coef, h["used"], self.batch, self.size,
+                              self.is_crop, self._max_h, self._workspace, self.device)
         h["sent"] = None
         self.step += 1
         self._submit(self.step)

@@ -220,6 +220,29 @@ int es_aug_fixmatch_u8(const uint8_t* frames, size_t frames_bytes, const void* e
 int es_aug_strong_u8(const uint8_t* weak, const void* entries, int n, int S, uint8_t* strong, void* workspace,
                      size_t workspace_bytes, hipStream_t stream);
 
+/* TransformCoMatch (code/dataset.py:58-110) and the labeled train transform (:185-196) the same way: entries = n
+ * EsAugCoEntry / EsAugLabEntry (esh_comatch_device_plan / esh_labeled_device_plan), every other argument, the
+ * refusals and the skipping of bad entries as in the fixmatch call; no output may be NULL.
+ *   comatch (4 launches): both resize passes once, the vertical one writing the unflipped base and the weak view
+ *     with its flip; strong_0 = the strong chain of the base (crop window = the image); strong_1 = the jitter chain.
+ *   labeled (3 launches): the vertical pass keeps the whole R x R image; one gather makes the S x S CenterCrop
+ *     window of the flipped, rotated image (Pillow's 16.16 walk, black outside); then the jitter chain.
+ * The jitter chain (up to four ColorJitter ops in the plan's order, RandomGrayscale, the flip) includes
+ * ColorJitter's hue: Pillow's HSV round trip per pixel, in the host's float / double types with IEEE division,
+ * fmod, floor and round.  es_aug_jitter_u8 runs that chain alone from S x S planar views x under n EsAugJitter
+ * plans (4-byte aligned) into out (not x itself); it needs no workspace. */
+size_t es_aug_comatch_entry_size(void);
+size_t es_aug_labeled_entry_size(void);
+size_t es_aug_comatch_workspace(int n, int S, int is_crop, int max_w, int max_h);
+size_t es_aug_labeled_workspace(int n, int S, int is_crop, int max_w, int max_h);
+int es_aug_comatch_u8(const uint8_t* frames, size_t frames_bytes, const void* entries, const int32_t* coeffs,
+                      size_t coeff_count, int n, int S, int is_crop, int max_h, uint8_t* weak, uint8_t* strong0,
+                      uint8_t* strong1, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int es_aug_labeled_u8(const uint8_t* frames, size_t frames_bytes, const void* entries, const int32_t* coeffs,
+                      size_t coeff_count, int n, int S, int is_crop, int max_h, uint8_t* out, void* workspace,
+                      size_t workspace_bytes, hipStream_t stream);
+int es_aug_jitter_u8(const uint8_t* x, const void* plans, int n, int S, uint8_t* out, hipStream_t stream);
+
 
 /* ---- ViT ends: patches, CLS/pos rows, embedding backward, final LN + head on CLS ------------- */
 int es_patch_im2col(const float* img, void* patches, int n, int S, int P, hipStream_t stream);

@@ -87,6 +87,33 @@ int esh_copy_frames(const uint8_t* const* srcs, const int* ws, const int* hs, in
 int esh_fixmatch_device_plan(const int* ws, const int* hs, const int64_t* frame_offs, int n, int S, int is_crop,
                              uint64_t seed, void* entries, int32_t* coeffs, size_t coeff_cap, size_t* coeff_used);
 
+/* The plans of esh_transform_batch(kind 2), TransformCoMatch (entries [n] EsAugCoEntry), and of kind 1, the
+ * labeled train transform (entries [n] EsAugLabEntry): the signature, the refusals and the NULL-coeffs /
+ * too-small-capacity sizing protocol of esh_fixmatch_device_plan.  The draws are the batch builder's own streams
+ * in their own order.  CoMatch: weak flip; strong_0's flip, both op indices, per op magnitude, apply, sign (only
+ * when applied), the two Cutout uniforms; strong_1's RandomApply draw, then (only when applied) three
+ * Fisher-Yates draws, the brightness / contrast / saturation factors as (float)(0.6 + 0.8 u) and the hue factor,
+ * resolved to (int)(f * 255.0); the grayscale draw; the flip.  Labeled: hflip, vflip, the angle (resolved for the
+ * R x R image as Image.rotate resolves it), two Fisher-Yates draws, one factor (float)(0.8 + 0.4 u) per position. */
+int esh_comatch_entry_size(void); /* sizeof(EsAugCoEntry) */
+int esh_labeled_entry_size(void); /* sizeof(EsAugLabEntry) */
+int esh_comatch_device_plan(const int* ws, const int* hs, const int64_t* frame_offs, int n, int S, int is_crop,
+                            uint64_t seed, void* entries, int32_t* coeffs, size_t coeff_cap, size_t* coeff_used);
+int esh_labeled_device_plan(const int* ws, const int* hs, const int64_t* frame_offs, int n, int S, int is_crop,
+                            uint64_t seed, void* entries, int32_t* coeffs, size_t coeff_cap, size_t* coeff_used);
+
+/* One EsAugJitter from explicit draws: order = nops (3 or 4) distinct ops (0 brightness, 1 contrast, 2 saturation,
+ * 3 hue, the last only with nops 4), factors = the three blend factors, hue_factor = adjust_hue's argument in
+ * [-0.5, 0.5].  2 on anything else. */
+int esh_jitter_plan_from_draws(int applied, int nops, const int* order, const float* factors, double hue_factor,
+                               int gray, int flip, void* jitter);
+
+/* The transform fields of one EsAugLabEntry from explicit draws: the flips, the rotation angle in degrees (an
+ * exact 90 / 180 / 270 is refused with 2: Pillow transposes there), a three-op jitter chain.  The frame and
+ * resize fields are zeroed (no tables); crop is CenterCrop's for (S, is_crop). */
+int esh_labeled_plan_from_draws(int S, int is_crop, int hflip, int vflip, double angle_deg, const int* order,
+                                const float* factors, void* entry);
+
 #ifdef __cplusplus
 }
 #endif
