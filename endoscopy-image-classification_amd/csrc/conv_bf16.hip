@@ -484,6 +484,129 @@ __global__ __launch_bounds__(256) void convb_nt_ring_kernel(NTConv a) {
   nt_tail<BN, DX, STATS, TO>(a, acc, M, m0, n0, Hm, Wm, om, oa0, ob0, smem);
 }
 
+// ---- direct 1 x 1 convolution ------------------------------------------------------------------
+// A 1 x 1 stride-1 unpadded conv over a dense NHWC bf16 map is the NT GEMM out[M, Ncol] = src[M, C] . wp[Ncol, C]^T
+// with M = N H W (forward: src = x and wp = the forward image; data gradient: src = dy and wp = the transposed
+// image, [Cin][Cout] for one tap).  No taps, no pixel decomposition, no padding: a thread's operand loads are
+// row-major 16-byte buffer loads at (row C + k) -- NTConv's N carries M, its Hs / Ws / kh / kw are 1.  64-deep K
+// steps (half the barriers of the implicit kernels' 32), each stored as two of the staged kernel's 32-channel LDS
+// images, so the fragment reads, the MFMA order and nt_tail are the implicit kernels': the outputs and the
+// BatchNorm partials are theirs bit for bit.  Edges: a row past M, a weight row past Ncol and the second half of a
+// last step when C % 64 == 32 are out-of-range buffer offsets (zeros); nt_tail stores rows < M, columns < Ncol.
+template <int BN, bool STATS, typename TO, bool INBN>
+__global__ __launch_bounds__(256) void convb_1x1_kernel(NTConv a) {
+  constexpr int NF = BN / 32;
+  constexpr int BJ = BN / 32;                   // weight chunks per thread per step (BN rows x 8 chunks / 256)
+  constexpr int AH = NT_BM * 64, BH = BN * 64;  // one 32-channel half of the A / B tile
+  constexpr int STAGE = 2 * (AH + BH);
+  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
+
+  const int M = a.N, C = a.C;
+  const int m0 = blockIdx.x * NT_BM, n0 = blockIdx.y * BN;
+  const int nk = (C + 63) / 64;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int g = lane >> 4, r = lane & 15;
+
+  // load slots: 8 lanes per row (one 16-byte chunk of the step's 128-byte run each), rows row0 + 32 j
+  const int ck = tid & 7, row0 = tid >> 3;
+  const __amdgpu_buffer_rsrc_t srs = buf_rsrc(a.src, a.sbytes), wrs = buf_rsrc(a.wp, a.wbytes);
+  unsigned aoff[4], boff[BJ];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int m = m0 + row0 + 32 * j;
+    aoff[j] = m < M ? (unsigned)(((long)m * C + ck * 8) * 2) : ES_OOB;
+  }
+#pragma unroll
+  for (int j = 0; j < BJ; ++j) {
+    const int col = n0 + row0 + 32 * j;
+    boff[j] = col < a.Ncol ? (unsigned)(((long)col * C + ck * 8) * 2) : ES_OOB;
+  }
+
+  u32x4 ra[4], rb[BJ];
+  f32x4 bm[2], br[2], bg[2], bb[2];  // INBN: the BatchNorm of this thread's 8 channels of the step
+  bool kok = true;
+  auto load = [&](int kt) {
+    const int k0 = kt * 64;
+    kok = k0 + ck * 8 < C;
+    if constexpr (INBN) {
+      const int cq = kok ? k0 + ck * 8 : 0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        bm[h] = *(const f32x4*)(a.bnm + cq + 4 * h);
+        br[h] = *(const f32x4*)(a.bnr + cq + 4 * h);
+        bg[h] = *(const f32x4*)(a.bng + cq + 4 * h);
+        bb[h] = *(const f32x4*)(a.bnb + cq + 4 * h);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      ra[j] = buf_load16(srs, (kok && aoff[j] != ES_OOB) ? aoff[j] + (unsigned)(k0 * 2) : ES_OOB);
+#pragma unroll
+    for (int j = 0; j < BJ; ++j)
+      rb[j] = buf_load16(wrs, (kok && boff[j] != ES_OOB) ? boff[j] + (unsigned)(k0 * 2) : ES_OOB);
+  };
+  auto store = [&](int buf) {
+    char* As = smem + buf * STAGE + (ck >> 2) * AH;
+    char* Bs = smem + buf * STAGE + 2 * AH + (ck >> 2) * BH;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int row = row0 + 32 * j;
+      u32x4 v = ra[j];
+      if constexpr (INBN) {  // relu(bn(x)) rounded to the map's type, as bn() stores it; rows past M stay zero
+        const bf16x8 x8 = __builtin_bit_cast(bf16x8, v);
+        const bf16x4 lo = q4_bn_relu(bf16x4{x8[0], x8[1], x8[2], x8[3]}, bm[0], br[0], bg[0], bb[0]);
+        const bf16x4 hi = q4_bn_relu(bf16x4{x8[4], x8[5], x8[6], x8[7]}, bm[1], br[1], bg[1], bb[1]);
+        v = (kok && aoff[j] != ES_OOB) ? __builtin_bit_cast(u32x4, cat8(lo, hi)) : u32x4{0u, 0u, 0u, 0u};
+      }
+      *(u32x4*)(As + row * 64 + cswz64(row, ck & 3) * 16) = v;
+    }
+#pragma unroll
+    for (int j = 0; j < BJ; ++j) {
+      const int row = row0 + 32 * j;
+      *(u32x4*)(Bs + row * 64 + cswz64(row, ck & 3) * 16) = rb[j];
+    }
+  };
+
+  const int wm = w >> 1, wn = w & 1;
+  f32x4 acc[4][NF];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  load(0);
+  store(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = kt & 1;
+    if (kt + 1 < nk) load(kt + 1);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const char* As = smem + buf * STAGE + h * AH;
+      const char* Bs = smem + buf * STAGE + 2 * AH + h * BH;
+      bf16x8 af[4], bfr[NF];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int rr = wm * 64 + i * 16 + r;
+        af[i] = *(const bf16x8*)(As + rr * 64 + cswz64(rr, g) * 16);
+      }
+#pragma unroll
+      for (int j = 0; j < NF; ++j) {
+        const int rr = wn * (BN / 2) + j * 16 + r;
+        bfr[j] = *(const bf16x8*)(Bs + rr * 64 + cswz64(rr, g) * 16);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < NF; ++j) acc[i][j] = mfma16(bfr[j], af[i], acc[i][j]);
+    }
+    if (kt + 1 < nk) store(buf ^ 1);
+    __syncthreads();
+  }
+
+  nt_tail<BN, false, STATS, TO>(a, acc, M, m0, n0, 1, 1, 1, 0, 0, smem);
+}
+
 // ---- weight gradient -------------------------------------------------------------------------
 struct DWConv {
   const void* x;    // [N, H, W, Cin] at (sxn, sxh, sxw), channel stride 1 (fp32 or bf16 map)
@@ -904,9 +1027,102 @@ void launch_dw_bn(dim3 grid, int flags, const DWConv& a, hipStream_t stream) {
   else launch_dw<B1, B2, false>(grid, flags, a, stream);
 }
 
+// the direct 1 x 1 kernels (convb_1x1_kernel): 0 = never, 1 = reductions at least ES_1X1_MIN_DEPTH deep, 2 = every
+// shape they can take; es_set_conv_1x1.  Isolated over ResNet-50's twelve stride-1 1 x 1 shapes at 224^2, N = 64
+// (scripts/conv1x1_bench.py, interleaved with the implicit kernels; DESIGN.md has the table): with a reduction depth
+// (forward: Cin, data gradient: Cout) of 512 and more the direct kernel is faster in every pass of every shape by
+// more than the implicit kernel's spread (forward 8-21 %, with the input BatchNorm 7-25 %, data gradient 6-26 %); at
+// 256 it wins some shapes and loses others (-3 .. +10 %), at 64 / 128 it ties or loses up to 15 % (a 64-deep step
+// there is the whole reduction or half of it: nothing to pipeline, and its 48-64 KiB of LDS hold fewer tiles)
+static int g_conv_1x1 = 1;
+constexpr int ES_1X1_MIN_DEPTH = 512;
+
+template <int BN, bool STATS, bool INBN>
+void launch_1x1(dim3 grid, int flags, const NTConv& a, hipStream_t stream) {
+  if (flags & 2) hipLaunchKernelGGL((convb_1x1_kernel<BN, STATS, bf16, INBN>), grid, 256, 0, stream, a);
+  else hipLaunchKernelGGL((convb_1x1_kernel<BN, STATS, float, INBN>), grid, 256, 0, stream, a);
+}
+template <int BN>
+void launch_1x1_any(dim3 grid, int flags, const NTConv& a, hipStream_t stream) {
+  if (a.bnm) {
+    if (a.stats) launch_1x1<BN, true, true>(grid, flags, a, stream);
+    else launch_1x1<BN, false, true>(grid, flags, a, stream);
+  } else {
+    if (a.stats) launch_1x1<BN, true, false>(grid, flags, a, stream);
+    else launch_1x1<BN, false, false>(grid, flags, a, stream);
+  }
+}
+
+// out[M, Ncol] (+)= bias + src[M, C] . w[Ncol, C]^T on the direct kernel; the tile choice is the implicit kernels'
+// (128 channels, 64 on a small grid), so the BatchNorm partials have their layout
+int conv1x1_impl(const void* src, int M, int C, const void* w, const float* bias, int Ncol, void* out, int accumulate,
+                 float* stats, int flags, const float* bnm, const float* bnr, const float* bng, const float* bnb,
+                 hipStream_t stream) {
+  if (!src || !w || !out) return ES_BAD_ARG;
+  if (M <= 0 || C <= 0 || Ncol <= 0 || C % 32 || Ncol % 32 || (flags & ~3) || !(flags & 1)) return ES_BAD_SHAPE;
+  const long sb = (long)M * C * 2, wb = (long)Ncol * C * 2;
+  if (sb >= 0x7fff0000L || wb >= 0x7fff0000L) return ES_BAD_SHAPE;
+  if (!al16(src) || !al16(w) || !al16(out) || (bias && !al16(bias))) return ES_BAD_SHAPE;
+  if (bnm && (!bnr || !bng || !bnb || !al16(bnm) || !al16(bnr) || !al16(bng) || !al16(bnb))) return ES_BAD_ARG;
+  if (stats && accumulate) return ES_BAD_ARG;
+  NTConv a{src, (const bf16*)w, bias, out, M, C, Ncol, 1, 1, (long)C, (long)C, (long)C, 1, 1, 1, 0, 1, 1,
+           (long)Ncol, (long)Ncol, (long)Ncol, accumulate, stats, bnm, bnr, bng, bnb, 1, (unsigned)sb, (unsigned)wb};
+  const dim3 g128((M + 127) / 128, Ncol / 128), g64((M + 127) / 128, (Ncol + 63) / 64);
+  if (Ncol % 128 == 0 && !conv_small_grid((long)g128.x * g128.y)) launch_1x1_any<128>(g128, flags, a, stream);
+  else launch_1x1_any<64>(g64, flags, a, stream);
+  return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
+}
+
 }  // namespace
 
 extern "C" {
+
+// tuning knob: the direct 1 x 1 kernels for 0 = no conv, 1 (default) = the shape class where they measured faster
+// than the implicit kernels (a reduction 512 deep or more), 2 = every conv they can take (bit-identical outputs
+// either way); returns the previous value, or ES_BAD_ARG (unchanged) for any other value
+int es_set_conv_1x1(int v) {
+  if (v < 0 || v > 2) return ES_BAD_ARG;
+  const int old = g_conv_1x1;
+  g_conv_1x1 = v;
+  return old;
+}
+
+// 1 when a 1 x 1 stride-1 unpadded conv over a dense bf16 map of M pixels goes to the direct kernel (kind 0 =
+// forward, 1 = forward with the input BatchNorm, 2 = data gradient; Cin / Cout the conv's), else 0
+int es_conv1x1_bf16_select(int kind, int M, int Cin, int Cout) {
+  if (kind < 0 || kind > 2 || !g_conv_1x1 || M <= 0 || Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 32) return 0;
+  const int C = kind == 2 ? Cout : Cin, Ncol = kind == 2 ? Cin : Cout;  // reduction depth, output channels
+  if ((long)M * C * 2 >= 0x7fff0000L || (long)Ncol * C * 2 >= 0x7fff0000L) return 0;
+  return g_conv_1x1 == 2 || C >= ES_1X1_MIN_DEPTH;
+}
+
+// y[M, Cout] (+)= bias + x[M, Cin] . wp[Cout, Cin]^T: es_conv2d_fwd_bf16_ex for a 1 x 1 stride-1 unpadded conv over
+// a dense NHWC bf16 map of M = N H W pixels (flags bit 0 must be set; bit 1 = y is a bf16 map), same outputs and
+// the same bn_partials (es_conv2d_bnstats_size(M, Cout) floats, nullable, accumulate 0 only) bit for bit
+int es_conv1x1_fwd_bf16_ex(const void* x, int M, int Cin, const void* wp, const float* bias, int Cout, void* y,
+                           int accumulate, float* bn_partials, int flags, hipStream_t stream) {
+  return conv1x1_impl(x, M, Cin, wp, bias, Cout, y, accumulate, bn_partials, flags, nullptr, nullptr, nullptr, nullptr,
+                      stream);
+}
+
+// es_conv1x1_fwd_bf16_ex whose input map is a train-mode BatchNorm + ReLU's INPUT (es_conv2d_fwd_bf16_bnin_ex's
+// contract: relu((x - mean) rstd gamma + beta) rounded to the map's type as the rows are loaded)
+int es_conv1x1_fwd_bf16_bnin_ex(const void* x, int M, int Cin, const void* wp, const float* bias, int Cout, void* y,
+                                int accumulate, float* bn_partials, int flags, const float* in_mean,
+                                const float* in_rstd, const float* in_gamma, const float* in_beta,
+                                hipStream_t stream) {
+  if (!in_mean) return ES_BAD_ARG;
+  return conv1x1_impl(x, M, Cin, wp, bias, Cout, y, accumulate, bn_partials, flags, in_mean, in_rstd, in_gamma, in_beta,
+                      stream);
+}
+
+// dx[M, Cin] (+)= dy[M, Cout] . wt[Cin, Cout]^T with wt = es_conv2d_pack_bf16's transposed image: the data gradient
+// of the same conv (flags bit 0 = dy is a bf16 map, required; bit 1 = dx is a bf16 map)
+int es_conv1x1_bwd_data_bf16_ex(const void* dy, int M, int Cout, const void* wt, int Cin, void* dx, int accumulate,
+                                int flags, hipStream_t stream) {
+  return conv1x1_impl(dy, M, Cout, wt, nullptr, Cin, dx, accumulate, nullptr, flags, nullptr, nullptr, nullptr, nullptr,
+                      stream);
+}
 
 // 1 if the bf16 kernels take a conv of these channel counts (both multiples of 32)
 // tuning knob: the workgroup count the bf16 weight gradient's automatic pixel split aims at (default 512);

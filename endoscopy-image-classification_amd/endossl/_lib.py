@@ -141,6 +141,11 @@ SIGNATURES = {
     "es_conv2d_fwd_bf16_bnin_ex": (I, [V, I, I, I, I, L, L, L, L, V, V, I, I, I, I, I, V, L, L, L, I, V, I, V, V, V, V, V]),
     "es_conv2d_bwd_weight_bf16_bnin_ex": (I, [V, I, I, I, I, L, L, L, L, V, L, L, L, I, I, I, I, I, I, V, V, I, I,
                                              V, V, V, V, V]),
+    "es_conv1x1_fwd_bf16_ex": (I, [V, I, I, V, V, I, V, I, V, I, V]),
+    "es_conv1x1_fwd_bf16_bnin_ex": (I, [V, I, I, V, V, I, V, I, V, I, V, V, V, V, V]),
+    "es_conv1x1_bwd_data_bf16_ex": (I, [V, I, I, V, I, V, I, I, V]),
+    "es_set_conv_1x1": (I, [I]),
+    "es_conv1x1_bf16_select": (I, [I, I, I, I]),
     "es_chan_sum_ex": (I, [V, I, I, L, L, I, V, V, I, I, V]),
     "es_set_bn_cs": (I, [I]),
     "es_set_bn_sum8": (I, [I]),

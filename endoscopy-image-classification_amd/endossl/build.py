@@ -12,32 +12,38 @@ default 256-d embedding.
 For 'conformer' it returns the native Conformer-Ti of code/build.py:135-142 (patch 16,
 channel_ratio 1, embed 384, depth 12, 6 heads, qkv_bias; conformer.NativeConformer, forward ->
 (conv_logits, trans_logits)) -- SemiFormer's backbone.  With MODEL.MARGIN set (code/build.py:173-174, checked
-first) `resnet18` gives resnet.ModelMargin, the ResNet-18 with a bias-free fc that the angular-margin step reads;
-a margin with any other backbone raises (ModelMargin needs `.fc`) unless IS_TRIPLET is set too, which the trainer
-tests first and which keeps building the plain backbone.  Other CNN / Swin backbones are outside the
-hot path.
+first) `resnet18` / `resnet50` give resnet.ModelMargin, the ResNet with a bias-free fc that the angular-margin step
+reads; a margin with any other backbone raises (ModelMargin needs `.fc`) unless IS_TRIPLET is set too, which the
+trainer tests first and which keeps building the plain backbone.
+`resnet18` and `resnet50` (the backbone ten of the reference's eighteen configs name) give resnet.NativeResNet with
+timm's state_dict -- for FixMatch and for the plain supervised mode.  The modes that wrap the backbone in ModelwEmb
+(CoMatch, IS_TRIPLET without SSL, EZBM) need an embedding head over a CNN trunk, which is not built: they raise for
+the ResNets instead of returning a logits-only model.  Other CNN / Swin backbones are outside the hot path
+(SURVEY.md §2 rows 6, 18).
 """
 import torch
 
 from .comatch_model import NativeViTEmb
 from .conformer import ConformerConfig, NativeConformer
-from .resnet import ModelMargin, NativeResNet, ResNetConfig
+from .resnet import RESNET50, ModelMargin, NativeResNet, ResNetConfig
 from .vit import VIT_CONFIGS, NativeViT, ViTConfig
 
 TRIPLET_LOW_DIM = 256  # ModelwEmb's default low_dim (code/models/custom_model.py:147)
+RESNETS = {"resnet18": {}, "resnet50": RESNET50}  # ResNetConfig arguments per timm name
 
 def build_model(config, is_pathology=True, seed=0):
     name = config.MODEL.NAME
     C = int(config.MODEL.NUM_CLASSES)
     if name != "conformer" and str(getattr(config.MODEL, "MARGIN", "None")) != "None":
         # code/build.py:173-174: checked before IS_SSL / IS_TRIPLET / PRE_TRAIN_PATH, none of which is read here
-        if name == "resnet18":
-            return ModelMargin(ResNetConfig(num_classes=C, fc_bias=False), seed=seed)
+        if name in RESNETS:
+            return ModelMargin(ResNetConfig(num_classes=C, fc_bias=False, **RESNETS[name]), seed=seed)
         # With IS_TRIPLET also set the trainer never reads the margin (code/supervised.py:84 tests the triplet
         # first): such a config keeps building the plain backbone below, as before the margin mode existed.
         if not getattr(config.MODEL, "IS_TRIPLET", False):
             raise NotImplementedError(f"MODEL.MARGIN with backbone {name!r}: ModelMargin needs a backbone with a .fc "
-                                      "classifier (code/models/custom_model.py:129); the native one is resnet18")
+                                      "classifier (code/models/custom_model.py:129); the native ones are resnet18 and "
+                                      "resnet50")
     if name == "conformer":
         img = int(config.DATA.IMG_SIZE) if "IMG_SIZE" in config.DATA else 224
         model = NativeConformer(ConformerConfig(img_size=img, patch=16, channel_ratio=1, embed_dim=384, depth=12,
@@ -50,13 +56,25 @@ def build_model(config, is_pathology=True, seed=0):
                   or v.shape[0] == C}
             model.load_state_dict(sd, strict=False)
         return model
-    if name == "resnet18":
+    if name in RESNETS:
         # the supervised baseline (BASELINE configs[0]; code/build.py:218-220 timm.create_model('resnet18',
-        # num_classes=C): ImageNet weights are a download, unavailable here -- timm's random init)
+        # num_classes=C): ImageNet weights are a download, unavailable here -- timm's random init) and resnet50,
+        # FixMatch's (code/build.py:196-197) and the supervised mode's backbone in most reference configs
+        if name != "resnet18":
+            # code/build.py:175-178,198-200 wrap the backbone in ModelwEmb (logits, fts, z) -- checked before
+            # PRE_TRAIN_PATH there too; the triplet step and both EZBM stages read fts / z
+            ssl = bool(getattr(config.TRAIN, "IS_SSL", True))
+            mode = ("TYPE_SEMI 'CoMatch'" if ssl and getattr(config.MODEL, "TYPE_SEMI", "FixMatch") == "CoMatch" else
+                    "IS_TRIPLET without IS_SSL (the triplet mode, EZBM)"
+                    if not ssl and getattr(config.MODEL, "IS_TRIPLET", False) else None)
+            if mode is not None:
+                raise NotImplementedError(f"{name} for {mode}: ModelwEmb (code/models/custom_model.py:136-213) over "
+                                          "a CNN trunk is not built -- the native embedding-head models are the "
+                                          f"ViTs; {name} is native for FixMatch, plain supervised and MODEL.MARGIN")
         if getattr(config.MODEL, "PRE_TRAIN_PATH", "None") not in (None, "None", ""):
-            raise NotImplementedError("resnet18 + PRE_TRAIN_PATH swaps fc for build_head's MLP "
+            raise NotImplementedError(f"{name} + PRE_TRAIN_PATH swaps fc for build_head's MLP "
                                       "(code/build.py:202-211): outside the native scope")
-        return NativeResNet(ResNetConfig(num_classes=C), seed=seed)
+        return NativeResNet(ResNetConfig(num_classes=C, **RESNETS[name]), seed=seed)
     if name not in VIT_CONFIGS:
         raise NotImplementedError(f"backbone {name!r}: native builds exist for {sorted(VIT_CONFIGS)}")
     comatch = getattr(config.MODEL, "TYPE_SEMI", "FixMatch") == "CoMatch" and getattr(config.TRAIN, "IS_SSL", True)

@@ -320,6 +320,13 @@ def _conv_bf16(m, xmap, Cout, k):
     return bool(_lib.load().es_conv2d_bf16_eligible(xmap.C, Cout, k, k))
 
 
+def _conv_1x1(m, x, xmap, k, s, p):
+    """A 1 x 1 stride-1 unpadded conv over a dense bf16 map of a model that opts in (`conv_1x1`: NativeResNet's
+    bottleneck configs) may run on the direct kernels (es_conv1x1_*; es_conv1x1_bf16_select decides per shape)."""
+    return bool(getattr(m, "conv_1x1", False) and k == 1 and s == 1 and p == 0 and x.dtype == torch.bfloat16
+                and xmap.sc == 1 and xmap.sw == xmap.C and xmap.sh == xmap.W * xmap.C and xmap.sn == xmap.H * xmap.sh)
+
+
 class _GradSink:
     """The gradient of a map with two consumers summed in place instead of by autograd's add (a full
     extra read-read-write pass over the map): a ConvBlock's input feeds conv1 and the residual
@@ -388,23 +395,27 @@ class _ConvFn(torch.autograd.Function):
         flags = _fl(x) | (_fl(y) << 1)
         args = (xmap.p(), xmap.N, xmap.H, xmap.W, xmap.C, xmap.sn, xmap.sh, xmap.sw, xmap.sc)
         tail = (ptr(m.pview(bname)) if bname else None, Cout, k, k, s, p, ptr(y), Ho * Wo * Cout, Wo * Cout, Cout, 0)
-        if b16 and stats and m.training and BN_STATS_FUSED and not (getattr(m, "sync_bn", True)
-                                                                    and dist.world_size() > 1):
-            # the BatchNorm that follows takes its batch statistics from these per-block partials (one
-            # rank's rows only: a SyncBatchNorm at N > 1 sums global statistics itself, _BNFn, so the
-            # partials are requested only when they will be consumed)
-            lib = _lib.load()
-            part = torch.empty(lib.es_conv2d_bnstats_size(xmap.N * Ho * Wo, Cout), device=x.device)
-            call("es_conv2d_fwd_bf16_ex", *args, ptr(m.conv_pack(wname, Cout, xmap.C, k)[0]), *tail, ptr(part), flags,
-                 _s())
-            m._bn_partials[y.data_ptr()] = (part, y.shape)
-        elif b16:
-            call("es_conv2d_fwd_bf16_ex", *args, ptr(m.conv_pack(wname, Cout, xmap.C, k)[0]), *tail, None, flags, _s())
+        d11 = b16 and _conv_1x1(m, x, xmap, k, s, p)
+        if b16:
+            lib, part, M = _lib.load(), None, xmap.N * Ho * Wo
+            if stats and m.training and BN_STATS_FUSED and not (getattr(m, "sync_bn", True) and dist.world_size() > 1):
+                # the BatchNorm that follows takes its batch statistics from these per-block partials (one
+                # rank's rows only: a SyncBatchNorm at N > 1 sums global statistics itself, _BNFn, so the
+                # partials are requested only when they will be consumed)
+                part = torch.empty(lib.es_conv2d_bnstats_size(M, Cout), device=x.device)
+            wp = m.conv_pack(wname, Cout, xmap.C, k)[0]
+            if d11 and lib.es_conv1x1_bf16_select(0, M, xmap.C, Cout):
+                call("es_conv1x1_fwd_bf16_ex", xmap.p(), M, xmap.C, ptr(wp), tail[0], Cout, ptr(y), 0, ptr(part), flags,
+                     _s())
+            else:
+                call("es_conv2d_fwd_bf16_ex", *args, ptr(wp), *tail, ptr(part), flags, _s())
+            if part is not None:
+                m._bn_partials[y.data_ptr()] = (part, y.shape)
         else:
             call("es_conv2d_fwd", *args, ptr(m.pview(wname)), *tail, _s())
         ctx.save_for_backward(x)
         ctx.m, ctx.xmap, ctx.spec, ctx.b16 = m, xmap, (wname, bname, Cout, k, s, p, Ho, Wo), b16
-        ctx.sink = sink
+        ctx.sink, ctx.d11 = sink, d11
         if CAPTURE is not None:
             CAPTURE("fwd", wname, _map_view(xmap.t, xmap), y, (bname, Cout, k, s, p, b16))
         return y
@@ -451,9 +462,13 @@ class _ConvFn(torch.autograd.Function):
             dx, acc = sink.take(alloc) if sink is not None else (alloc(), 0)
             wimg = m.conv_pack(wname, Cout, xm.C, k)[1] if b16 else m.pview(wname)
             before = _map_view(dx, xm).clone() if CAPTURE is not None and acc else None
-            call("es_conv2d_bwd_data_bf16_ex" if b16 else "es_conv2d_bwd_data", ptr(dy), Ho * Wo * Cout, Wo * Cout, Cout,
-                 ptr(wimg), xm.N, xm.H, xm.W, xm.C, Cout, k, k, s, p, ptr(dx) + dx.element_size() * xm.off, xm.sn, xm.sh,
-                 xm.sw, xm.sc, acc, *((_fl(dy) | (_fl(dx) << 1),) if b16 else ()), _s())
+            if ctx.d11 and dy.dtype == torch.bfloat16 and lib.es_conv1x1_bf16_select(2, M, xm.C, Cout):
+                call("es_conv1x1_bwd_data_bf16_ex", ptr(dy), M, Cout, ptr(wimg), xm.C,
+                     ptr(dx) + dx.element_size() * xm.off, acc, 1 | (_fl(dx) << 1), _s())
+            else:
+                call("es_conv2d_bwd_data_bf16_ex" if b16 else "es_conv2d_bwd_data", ptr(dy), Ho * Wo * Cout, Wo * Cout,
+                     Cout, ptr(wimg), xm.N, xm.H, xm.W, xm.C, Cout, k, k, s, p, ptr(dx) + dx.element_size() * xm.off,
+                     xm.sn, xm.sh, xm.sw, xm.sc, acc, *((_fl(dy) | (_fl(dx) << 1),) if b16 else ()), _s())
             if CAPTURE is not None:
                 CAPTURE("bwd", wname, dy, before, _map_view(dx, xm))
             if sink is not None:  # first consumer: hand the buffer over; second: return the sum
@@ -600,12 +615,17 @@ class _BNConvFn(torch.autograd.Function):
         part_out = None
         if stats and BN_STATS_FUSED:  # the next BatchNorm's statistics, as _ConvFn (train mode, world 1 here)
             part_out = torch.empty(_lib.load().es_conv2d_bnstats_size(N * Ho * Wo, Cout), device=x.device)
-        call("es_conv2d_fwd_bf16_bnin_ex", *args, ptr(m.conv_pack(wname, Cout, C, k)[0]), *tail,
-             ptr(part_out) if part_out is not None else None, flags, ptr(mean), ptr(rstd), ptr(gam), ptr(bet), _s())
+        d11 = _conv_1x1(m, x, xmap, k, s, p)
+        if d11 and _lib.load().es_conv1x1_bf16_select(1, rows, C, Cout):
+            call("es_conv1x1_fwd_bf16_bnin_ex", xmap.p(), rows, C, ptr(m.conv_pack(wname, Cout, C, k)[0]), tail[0],
+                 Cout, ptr(y), 0, ptr(part_out), flags, ptr(mean), ptr(rstd), ptr(gam), ptr(bet), _s())
+        else:
+            call("es_conv2d_fwd_bf16_bnin_ex", *args, ptr(m.conv_pack(wname, Cout, C, k)[0]), *tail,
+                 ptr(part_out) if part_out is not None else None, flags, ptr(mean), ptr(rstd), ptr(gam), ptr(bet), _s())
         if part_out is not None:
             m._bn_partials[y.data_ptr()] = (part_out, y.shape)
         ctx.save_for_backward(x, mean, rstd)
-        ctx.m, ctx.pre, ctx.spec = m, pre, (wname, bname, Cout, k, s, p, Ho, Wo)
+        ctx.m, ctx.pre, ctx.spec, ctx.d11 = m, pre, (wname, bname, Cout, k, s, p, Ho, Wo), d11
         return y
 
     @staticmethod
@@ -636,8 +656,13 @@ class _BNConvFn(torch.autograd.Function):
                 call("es_chan_sum_ex", ptr(dy), M, Cout, M * Cout, Cout, M, ptr(wsb), ptr(m.gview(bname)), 0, _fl(dy),
                      _s())
         dh = torch.empty_like(x)  # d(loss) / d(BN output): every pixel written (all stride phases)
-        call("es_conv2d_bwd_data_bf16_ex", ptr(dy), Ho * Wo * Cout, Wo * Cout, Cout, ptr(m.conv_pack(wname, Cout, C, k)[1]),
-             N, H, W, C, Cout, k, k, s, p, ptr(dh), H * W * C, W * C, C, 1, 0, _fl(dy) | (_fl(dh) << 1), _s())
+        if ctx.d11 and dy.dtype == torch.bfloat16 and lib.es_conv1x1_bf16_select(2, M, C, Cout):
+            call("es_conv1x1_bwd_data_bf16_ex", ptr(dy), M, Cout, ptr(m.conv_pack(wname, Cout, C, k)[1]), C, ptr(dh), 0,
+                 1 | (_fl(dh) << 1), _s())
+        else:
+            call("es_conv2d_bwd_data_bf16_ex", ptr(dy), Ho * Wo * Cout, Wo * Cout, Cout,
+                 ptr(m.conv_pack(wname, Cout, C, k)[1]), N, H, W, C, Cout, k, k, s, p, ptr(dh), H * W * C, W * C, C, 1,
+                 0, _fl(dy) | (_fl(dh) << 1), _s())
         dx = torch.empty_like(x)
         wsn = torch.empty(lib.es_chan_workspace(rows, C), device=x.device)
         call("es_bn2d_bwd_recompute_ex", ptr(x), ptr(dh), rows, C, ptr(gam), ptr(bet), ptr(mean), ptr(rstd), ptr(dx),

@@ -27,6 +27,7 @@ import torch
 
 from . import _lib, dist
 from ._lib import call, ptr
+from .conformer import join_wgrad_stream
 from .loss import ce_loss
 from .trainer import Trainer, _next  # noqa: F401  (_next: imported from here by callers)
 from .utils import AverageMeter
@@ -48,6 +49,11 @@ class FixMatch(Trainer):
         self.epoch_start = 1
         self._dlogits = None
         self._stats = None
+        # a CNN backbone (resnet.NativeResNet: no ViT engine, autograd over the conv / BatchNorm Functions) steps
+        # through _step_cnn, and its BatchNorm running buffers are blended into the EMA model
+        self.cnn = not hasattr(model, "engine")
+        if self.cnn:
+            self.EMA_BUFFERS = True
 
     def _trainable_when_frozen(self):
         """The modules IS_FREEZE keeps trainable (code/fixmatch.py:45-48: `model.fc`)."""
@@ -63,6 +69,8 @@ class FixMatch(Trainer):
         if self.frozen:
             for mod in self._trainable_when_frozen():
                 mod.requires_grad_(True)
+        if self.cnn:  # the trunk off the autograd tape: the head's backward alone (as SemiFormer's IS_FREEZE)
+            self.model.frozen_trunk = self.frozen
         self._setup_model(config)
         self._setup_optim(config, config.TRAIN.EVAL_STEP, self.train_labeled_dl)
 
@@ -145,8 +153,47 @@ class FixMatch(Trainer):
         self._graph.replay()
         return self._gstats
 
+    def _step_cnn(self, batch):
+        """The step over a CNN backbone (NativeResNet): the reference's ONE train-mode forward over
+        cat(x, u_w, u_s) (code/fixmatch.py:107-112).  BatchNorm couples the rows of a batch, so the weak rows are
+        not split off into an inference pass as they are for the ViT: they shape the batch statistics and the
+        running buffers, and although their logits are detached (code/loss.py:144: zero rows of dlogits) the
+        BatchNorm backward still sends them a gradient.  Same fused losses, autograd through the trunk."""
+        (inputs_x, targets_x), ((inputs_u_w, inputs_u_s), _) = batch
+        m, cfg = self.model, self.config
+        dev = m.flat.device
+        self._inflight.wait()
+        B, nu = int(inputs_x.shape[0]), int(inputs_u_w.shape[0])
+        targets_x = targets_x.to(dev, non_blocking=True).to(torch.int64).contiguous()
+        inputs = torch.cat((inputs_x.to(dev, non_blocking=True), inputs_u_w.to(dev, non_blocking=True),
+                            inputs_u_s.to(dev, non_blocking=True)))
+        m.train()
+        out = m(inputs)
+        logits = out.detach()
+        C = int(logits.shape[1])
+        s = _lib.stream()
+        dl = torch.zeros_like(logits)
+        self._pl = torch.empty(nu, dtype=torch.int32, device=dev)
+        self._mask = torch.empty(nu, dtype=torch.uint8, device=dev)
+        stats = torch.empty(4, dtype=torch.float32, device=dev)  # lx, lu, mask_mean, total
+        call("es_poly_ce_fwd_bwd", ptr(logits), C, ptr(targets_x), ptr(self.class_weights), B, C, 2.0, 1.0 / B,
+             ptr(dl), C, ptr(stats[0:1]), s)
+        lam = float(cfg.TRAIN.LAMBDA_U)
+        call("es_fm_consistency_fwd_bwd", ptr(logits[B:B + nu]), C, ptr(logits[B + nu:]), C, nu, C,
+             float(cfg.TRAIN.THRES), lam / nu, ptr(self._pl), ptr(self._mask), None, ptr(dl[B + nu:]), C,
+             ptr(stats[1:3]), s)
+        torch.add(stats[0], stats[1], alpha=lam, out=stats[3])
+        self.optimizer.zero_grad()
+        torch.autograd.backward([out], [dl])
+        join_wgrad_stream(dev)
+        self._finish_step()
+        return {"loss": stats[3], "lx": stats[0], "lu": stats[1], "mask_mean": stats[2],
+                "pseudo_label": self._pl, "mask": self._mask}
+
     def step(self, batch):
         """batch = ((x, y), ((u_w, u_s), idx)) -> dict of device scalars / tensors."""
+        if self.cnn:
+            return self._step_cnn(batch)
         (inputs_x, targets_x), ((inputs_u_w, inputs_u_s), _) = batch
         dev = self.model.flat.device
         self._inflight.wait()

@@ -1,11 +1,15 @@
 """Native ResNet-18 -- the supervised baseline of BASELINE configs[0] (SURVEY.md §8(d) P0:
-`supervised.py` ResNet-18, 23 classes, B=16, 224²) on the Conformer's CNN kernels.
+`supervised.py` ResNet-18, 23 classes, B=16, 224²) -- and ResNet-50, the backbone most reference configs name
+(`code/configs/*`: `NAME: 'resnet50'`), on the Conformer's CNN kernels.
 
 Reference: `build_model` -> timm `resnet18` (`code/build.py:160-211`, timm==0.5.4, absent from this
 image: its architecture is restated here -- conv1 7x7/2 -> BatchNorm -> ReLU -> max-pool 3/2 -> four
 stages of two BasicBlocks (3x3 conv -> BN -> ReLU -> 3x3 conv -> BN, + identity or 1x1/2 conv + BN
 shortcut, ReLU) -> global average pool -> fc).  `model(x) -> logits`, the timm state_dict (names
-and order), so checkpoints interchange.
+and order), so checkpoints interchange.  resnet50 (`ResNetConfig(**RESNET50)`): the same stem and head around
+stages of 3 / 4 / 6 / 3 Bottlenecks (1x1 conv -> BN -> ReLU -> 3x3 conv with the stride -> BN -> ReLU -> 1x1 conv
+to 4x the width -> BN, + identity or 1x1 conv with the stride + BN shortcut, ReLU), fc over 2048 features;
+its stride-1 1x1 convs run on the direct kernels (es_conv1x1_*) where those are faster.
 
 MI355X layout (as NativeConformer, whose parameter plumbing it shares): parameters in one flat fp32
 buffer, NHWC maps, every conv an implicit GEMM (bf16 operands for channel counts % 32 == 0 --
@@ -31,20 +35,37 @@ BN_EPS = 1e-5  # timm BasicBlock norm_layer = nn.BatchNorm2d (default eps)
 
 
 class ResNetConfig:
-    def __init__(self, layers=(2, 2, 2, 2), num_classes=23, img_size=224, widths=(64, 128, 256, 512), fc_bias=True):
+    """The default is timm's resnet18 (BasicBlocks); `RESNET50` below is its resnet50 (Bottlenecks)."""
+
+    def __init__(self, layers=(2, 2, 2, 2), num_classes=23, img_size=224, widths=(64, 128, 256, 512), fc_bias=True,
+                 block="basic"):
+        if block not in ("basic", "bottleneck"):
+            raise ValueError(f"block {block!r}: 'basic' or 'bottleneck'")
         self.layers, self.widths = tuple(layers), tuple(widths)
         self.num_classes, self.img_size = num_classes, img_size
-        self.fc_bias = bool(fc_bias)  # False: ModelMargin's nn.Linear(512, C, bias=False)
+        self.fc_bias = bool(fc_bias)  # False: ModelMargin's nn.Linear(num_features, C, bias=False)
+        self.block = block
+        self.expansion = 4 if block == "bottleneck" else 1  # timm Bottleneck.expansion / BasicBlock.expansion
+
+    @property
+    def num_features(self):
+        """Channels of the last stage = the pooled feature width = fc's fan-in (512 | 2048)."""
+        return self.widths[-1] * self.expansion
 
     def blocks(self):
-        """(prefix, inplanes, planes, stride, downsample) per BasicBlock in state_dict order."""
+        """(prefix, inplanes, planes, stride, downsample) per block in state_dict order; a block's output has
+        planes * expansion channels."""
         out, inp = [], 64
         for si, (n, w) in enumerate(zip(self.layers, self.widths)):
             for bi in range(n):
                 stride = 2 if (si > 0 and bi == 0) else 1
-                out.append((f"layer{si + 1}.{bi}.", inp, w, stride, stride != 1 or inp != w))
-                inp = w
+                out.append((f"layer{si + 1}.{bi}.", inp, w, stride, stride != 1 or inp != w * self.expansion))
+                inp = w * self.expansion
         return out
+
+
+# timm resnet50: Bottleneck, layers [3, 4, 6, 3] -- stage outputs 256 / 512 / 1024 / 2048
+RESNET50 = dict(layers=(3, 4, 6, 3), widths=(64, 128, 256, 512), block="bottleneck")
 
 
 def _bn_entries(pre, C):
@@ -53,15 +74,22 @@ def _bn_entries(pre, C):
 
 
 def resnet_layout(cfg):
-    """(name, shape, kind) in timm resnet18's state_dict order."""
+    """(name, shape, kind) in timm resnet18's / resnet50's state_dict order."""
     out = [("conv1.weight", (64, 3, 7, 7), "p")] + _bn_entries("bn1.", 64)
+    bottleneck = getattr(cfg, "block", "basic") == "bottleneck"
     for pre, inp, w, stride, ds in cfg.blocks():
-        out += [(pre + "conv1.weight", (w, inp, 3, 3), "p")] + _bn_entries(pre + "bn1.", w)
-        out += [(pre + "conv2.weight", (w, w, 3, 3), "p")] + _bn_entries(pre + "bn2.", w)
+        outp = w * getattr(cfg, "expansion", 1)
+        if bottleneck:
+            out += [(pre + "conv1.weight", (w, inp, 1, 1), "p")] + _bn_entries(pre + "bn1.", w)
+            out += [(pre + "conv2.weight", (w, w, 3, 3), "p")] + _bn_entries(pre + "bn2.", w)
+            out += [(pre + "conv3.weight", (outp, w, 1, 1), "p")] + _bn_entries(pre + "bn3.", outp)
+        else:
+            out += [(pre + "conv1.weight", (w, inp, 3, 3), "p")] + _bn_entries(pre + "bn1.", w)
+            out += [(pre + "conv2.weight", (w, w, 3, 3), "p")] + _bn_entries(pre + "bn2.", w)
         if ds:
-            out += [(pre + "downsample.0.weight", (w, inp, 1, 1), "p")] + _bn_entries(pre + "downsample.1.", w)
+            out += [(pre + "downsample.0.weight", (outp, inp, 1, 1), "p")] + _bn_entries(pre + "downsample.1.", outp)
     C = cfg.num_classes
-    out += [("fc.weight", (C, cfg.widths[-1]), "p")]
+    out += [("fc.weight", (C, cfg.widths[-1] * getattr(cfg, "expansion", 1)), "p")]
     if getattr(cfg, "fc_bias", True):
         out += [("fc.bias", (C,), "p")]
     return out
@@ -69,7 +97,8 @@ def resnet_layout(cfg):
 
 def init_resnet_(flat, layout, offs, generator=None):
     """timm ResNet.init_weights: kaiming-normal (fan_out, ReLU) convs, BatchNorm weight 1 / bias 0,
-    fc as nn.Linear's default (uniform +-1/sqrt(fan_in) for weight and bias)."""
+    fc as nn.Linear's default (uniform +-1/sqrt(fan_in) for weight and bias).  Every BatchNorm weight is 1, a
+    block's last one (bn2 / bn3) included: timm's zero_init_last_bn is not restated."""
     fan_in = next(shape[1] for name, shape, _ in layout if name == "fc.weight")
     for name, shape, kind in layout:
         if kind != "p":
@@ -88,7 +117,8 @@ def init_resnet_(flat, layout, offs, generator=None):
 
 
 class NativeResNet(NativeConformer):
-    """ResNet-18 whose compute runs in libendossl_hip.so; state_dict identical to timm's resnet18.
+    """ResNet-18 / ResNet-50 whose compute runs in libendossl_hip.so; state_dict identical to timm's resnet18 /
+    resnet50.
     Shares NativeConformer's flat-parameter plumbing (views, BatchNorm buffers, bf16 conv images,
     device moves, deepcopy) and its conv / BatchNorm / pooling / head autograd Functions."""
 
@@ -127,8 +157,34 @@ class NativeResNet(NativeConformer):
     def _pack(self):  # no transformer weight images
         return None
 
+    @property
+    def conv_1x1(self):
+        """The stride-1 1 x 1 convs over dense bf16 maps on the direct kernels (es_conv1x1_*, where the library's
+        es_set_conv_1x1 knob selects them): the bottleneck configs, whose work is mostly such convs.  ResNet-18's
+        only 1 x 1 convs are its strided shortcuts: it keeps the implicit kernels."""
+        return self.cfg.block == "bottleneck"
+
+    def _bottleneck(self, x, pre, inp, planes, stride, ds):
+        """timm Bottleneck.forward: relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x)))))))) + shortcut), the stride on
+        conv2 (timm 0.5.4's resnet50), shortcut = x or downsample.1(downsample.0(x)) (1 x 1 conv with the stride).
+        Composed as the Conformer's ConvBlock (_conv_block_head / _conv_block_tail): bn1 + ReLU applied by conv2's
+        gathers only where BN_CONV_FUSED_KXK allows, bn2 + ReLU by conv3's loads (bn_conv)."""
+        outp = planes * self.cfg.expansion
+        sink = _GradSink() if GRAD_SINKS else None  # x's two gradient contributions summed in place
+        h = conv(self, x, _Map.nhwc(x), pre + "conv1.weight", None, planes, 1, 1, 0, stats=True, sink=sink)
+        h = bn_conv(self, h, pre + "bn1.", pre + "conv2.weight", None, planes, 3, stride, 1, stats=True, eps=BN_EPS)
+        h = bn_conv(self, h, pre + "bn2.", pre + "conv3.weight", None, outp, 1, 1, 0, stats=True, eps=BN_EPS)
+        if ds:
+            sc = conv(self, x, _Map.nhwc(x), pre + "downsample.0.weight", None, outp, 1, stride, 0, stats=True,
+                      sink=sink)
+            sc = bn(self, sc, pre + "downsample.1.", eps=BN_EPS)
+            return bn(self, h, pre + "bn3.", eps=BN_EPS, relu=True, res=sc)
+        return bn(self, h, pre + "bn3.", eps=BN_EPS, relu=True, res=x, res_sink=sink)
+
     def _block(self, x, pre, inp, planes, stride, ds):
-        """timm BasicBlock.forward: relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut)."""
+        """timm BasicBlock.forward: relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut); Bottleneck: _bottleneck."""
+        if self.cfg.block == "bottleneck":
+            return self._bottleneck(x, pre, inp, planes, stride, ds)
         sink = _GradSink() if GRAD_SINKS else None  # x's two gradient contributions summed in place
         h = conv(self, x, _Map.nhwc(x), pre + "conv1.weight", None, planes, 3, stride, 1, stats=True, sink=sink)
         # bn1 + ReLU feed conv2 alone: applied by conv2's gathers where the bf16 kernels run it (bn_conv)
@@ -221,14 +277,14 @@ class _LinearNoBiasFn(torch.autograd.Function):
 
 
 class ModelMargin(NativeResNet):
-    """ModelMargin over resnet18 (code/models/custom_model.py:122-134): the ResNet-18 with a bias-free fc, for
+    """ModelMargin over resnet18 or resnet50 (code/models/custom_model.py:122-134): the ResNet with a bias-free fc, for
     the angular-margin losses (loss.AngularPenaltySMLoss reads `fc.weight`, code/supervised.py:117-119).
 
       model(x)            plain logits fc(pool(trunk(x))), no normalisation (evaluate_one / inference)
-      model.backbone(x)   the pooled [n, 512] features, on the autograd tape in training mode
-      model.fc            the classifier module; `.weight` [C, 512] is a view of the flat buffer
+      model.backbone(x)   the pooled [n, F] features (F = 512 | 2048), on the autograd tape in training mode
+      model.fc            the classifier module; `.weight` [C, F] is a view of the flat buffer
 
-    state_dict: the reference's `model.*` keys (timm's resnet18 names under `model.`, `model.fc.weight`, no
+    state_dict: the reference's `model.*` keys (timm's resnet names under `model.`, `model.fc.weight`, no
     bias) followed by its `fc.weight` alias of the same tensor.  The reference also lists every trunk tensor a
     second time as `backbone.N.*` (nn.Sequential over timm's children): loading skips those keys, and they are
     not written -- timm is absent, so the index map N is unpinned."""

@@ -595,6 +595,28 @@ int es_conv2d_bwd_weight_bf16_bnin_ex(const void* x, int N, int H, int W, int Ci
                                       int stride, int pad, int splits, float* workspace, float* dw, int accumulate,
                                       int flags, const float* in_mean, const float* in_rstd, const float* in_gamma,
                                       const float* in_beta, hipStream_t stream);
+/* Direct 1 x 1 convolution (timm Bottleneck conv1 / conv3 / downsample.0 at stride 1: nn.Conv2d(k=1)).  A 1 x 1
+ * stride-1 unpadded conv over a dense NHWC bf16 map of M = N H W pixels is the NT GEMM y[M, Cout] = x[M, Cin] .
+ * wp[Cout, Cin]^T: these read the rows with plain row-major 16-byte loads instead of the implicit-GEMM gather.
+ * Same packed weights, same flags (bit 0, the input map is bf16, must be set), same outputs and the same
+ * bn_partials as es_conv2d_fwd_bf16_ex / _bnin_ex / es_conv2d_bwd_data_bf16_ex, bit for bit.  Maps and weights
+ * under 2 GiB each. */
+int es_conv1x1_fwd_bf16_ex(const void* x, int M, int Cin, const void* wp, const float* bias, int Cout, void* y,
+                           int accumulate, float* bn_partials, int flags, hipStream_t stream);
+int es_conv1x1_fwd_bf16_bnin_ex(const void* x, int M, int Cin, const void* wp, const float* bias, int Cout, void* y,
+                                int accumulate, float* bn_partials, int flags, const float* in_mean,
+                                const float* in_rstd, const float* in_gamma, const float* in_beta,
+                                hipStream_t stream);
+int es_conv1x1_bwd_data_bf16_ex(const void* dy, int M, int Cout, const void* wt, int Cin, void* dx, int accumulate,
+                                int flags, hipStream_t stream);
+/* tuning knob: the direct 1 x 1 kernels for 0 = no conv, 1 (default) = the shape class where they measured faster
+ * than the implicit kernels (a reduction 512 deep or more: forward Cin, data gradient Cout), 2 = every
+ * conv they can take; returns the previous value, or -2
+ * (unchanged) otherwise.  es_conv1x1_bf16_select: 1 when such a conv (kind 0 = forward, 1 = forward with the
+ * input BatchNorm, 2 = data gradient) goes to the direct kernel under the knob.  Callers ask only for models that
+ * opt in (resnet.NativeResNet bottleneck configs): every other model keeps the implicit kernels. */
+int es_set_conv_1x1(int v);
+int es_conv1x1_bf16_select(int kind, int M, int Cin, int Cout);
 int es_chan_sum_ex(const void* v, int rows, int C, long sn, long sp, int HW, float* workspace, float* out,
                    int accumulate, int flags, hipStream_t stream);
 /* tuning knob: 1 (default) = the channel-stationary BatchNorm apply kernels (forward apply and the backward's dx
