@@ -171,6 +171,17 @@ SIGNATURES = {
     "es_ce_weighted_fwd_bwd": (I, [V, I, V, V, I, I, F, V, I, V, V]),
     "es_ce_weight_sum": (I, [V, V, I, I, V, V]),
     "es_ce_weighted_fwd_bwd_global": (I, [V, I, V, V, V, I, I, F, V, I, V, V]),
+    # the squeeze-excite bottleneck tail (csrc/se.hip)
+    "es_se_bn_stats": (I, [V, V, I, I, F, F, I, V, V, V, V, V, V]),
+    "es_se_squeeze_workspace": (Z, [I, I, I, I]),
+    "es_se_bn_bwd_sums_workspace": (Z, [I, I, I, I]),
+    "es_se_gate_bwd_workspace": (Z, [I, I, I]),
+    "es_se_squeeze_ex": (I, [V, I, I, I, V, V, V, V, V, V, V, I, V]),
+    "es_se_gate_fwd": (I, [V, V, V, I, I, I, V, V, V]),
+    "es_se_bn_apply_ex": (I, [V, V, V, I, I, I, V, V, V, V, V, I, V]),
+    "es_se_bn_bwd_sums_ex": (I, [V, V, V, I, I, I, V, V, V, V, V, I, V]),
+    "es_se_gate_bwd": (I, [V, V, V, V, V, V, V, V, V, V, V, V, I, I, I, V, V, V, V, V, V, V]),
+    "es_se_bn_bwd_dx_ex": (I, [V, V, V, V, V, I, I, I, V, V, V, V, V, I, V, V, I, I, V]),
     "es_adam_ema_step": (I, [V, V, V, V, V, L, F, F, F, F, F, F, F, F, V]),
     "es_adamw_ema_step": (I, [V, V, V, V, V, V, L, F, F, F, F, F, F, F, F, F, F, F, F, F, V]),
     "es_sgd_ema_step": (I, [V, V, V, V, V, L, F, F, F, F, F, I, F, F, F, V]),

@@ -18,22 +18,54 @@ trainer tests first and which keeps building the plain backbone.
 `resnet18` and `resnet50` (the backbone ten of the reference's eighteen configs name) give resnet.NativeResNet with
 timm's state_dict -- for FixMatch and for the plain supervised mode.  The modes that wrap the backbone in ModelwEmb
 (CoMatch, IS_TRIPLET without SSL, EZBM) need an embedding head over a CNN trunk, which is not built: they raise for
-the ResNets instead of returning a logits-only model.  Other CNN / Swin backbones are outside the hot path
+the ResNets instead of returning a logits-only model.  `resnet50se` (code/build.py:152-170, the reference's own
+SEResNet, code/models/se.py) gives resnet.NativeSEResNet for FixMatch and the plain supervised mode, with the 2-class
+abnormality checkpoint of MODEL.PRE_TRAIN_PATH re-headed as the reference does; IS_TRIPLET, CoMatch and MARGIN raise
+for it.  Other CNN / Swin backbones are outside the hot path
 (SURVEY.md §2 rows 6, 18).
 """
 import torch
 
 from .comatch_model import NativeViTEmb
 from .conformer import ConformerConfig, NativeConformer
-from .resnet import RESNET50, ModelMargin, NativeResNet, ResNetConfig
+from .resnet import RESNET50, ModelMargin, NativeResNet, NativeSEResNet, ResNetConfig
 from .vit import VIT_CONFIGS, NativeViT, ViTConfig
 
 TRIPLET_LOW_DIM = 256  # ModelwEmb's default low_dim (code/models/custom_model.py:147)
 RESNETS = {"resnet18": {}, "resnet50": RESNET50}  # ResNetConfig arguments per timm name
 
+def _build_resnet50se(config, C, seed):
+    """code/build.py:152-170: SEResNet(Bottleneck, [3, 4, 6, 3]) (code/models/se.py) -> NativeSEResNet.  The branch is
+    tested before MARGIN / IS_SSL there; the modes whose trainer cannot use the logits-only model it builds raise."""
+    if getattr(config.MODEL, "IS_TRIPLET", False):  # :153-155
+        raise NotImplementedError("resnet50se for IS_TRIPLET: ModelwEmb (code/models/custom_model.py:136-213) over "
+                                  "a CNN trunk is not built -- the native embedding-head models are the ViTs; "
+                                  "resnet50se is native for FixMatch and plain supervised")
+    if getattr(config.TRAIN, "IS_SSL", True) and getattr(config.MODEL, "TYPE_SEMI", "FixMatch") == "CoMatch":
+        raise NotImplementedError("resnet50se for TYPE_SEMI 'CoMatch': the reference builds a logits-only SEResNet "
+                                  "(code/build.py:156-170) that its CoMatch trainer, which reads (logits, fts, z), "
+                                  "cannot use; ModelwEmb over a CNN trunk is not built")
+    if str(getattr(config.MODEL, "MARGIN", "None")) != "None":
+        raise NotImplementedError("resnet50se with MODEL.MARGIN: the reference ignores the margin at build "
+                                  "(code/build.py:152 precedes :173) and its trainer then fails on model.backbone; "
+                                  "the native ModelMargin backbones are resnet18 and resnet50")
+    model = NativeSEResNet(ResNetConfig(num_classes=C, se=True, **RESNET50), seed=seed)
+    path = getattr(config.MODEL, "PRE_TRAIN_PATH", "None")
+    if path not in (None, "None", ""):
+        # :158-165 loads the 2-class abnormality checkpoint and re-heads it (build_head: a plain Linear)
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        sd = ck.get("model_state_dict", ck)
+        if sd.get("fc.weight") is not None and sd["fc.weight"].shape[0] != C:
+            sd = {k: v for k, v in sd.items() if not k.startswith("fc.")}
+        model.load_state_dict(sd, strict=False)
+    return model
+
+
 def build_model(config, is_pathology=True, seed=0):
     name = config.MODEL.NAME
     C = int(config.MODEL.NUM_CLASSES)
+    if name == "resnet50se":
+        return _build_resnet50se(config, C, seed)
     if name != "conformer" and str(getattr(config.MODEL, "MARGIN", "None")) != "None":
         # code/build.py:173-174: checked before IS_SSL / IS_TRIPLET / PRE_TRAIN_PATH, none of which is read here
         if name in RESNETS:

@@ -18,6 +18,10 @@ and ReLU fused into its apply pass, SyncBatchNorm at N > 1 (as the Conformer).  
 the activation and gradient maps after the stem's max-pool are bf16 (map_bf16; the stem and BatchNorm
 statistics stay fp32, ENDOSSL_MAP_BF16=0 keeps fp32 maps): every conv after the stem is bf16-eligible.
 
+`NativeSEResNet` is the reference's own `resnet50se` (code/models/se.py:8-119, code/build.py:152-170): ResNet-50 with
+a squeeze-excite gate on bn3's output in every Bottleneck (`ResNetConfig(se=True)`: conv_down / conv_up per block).
+Only the block tail differs, and it runs on csrc/se.hip without writing bn3's output (`_SETailFn`).
+
 `ModelMargin` (code/models/custom_model.py:122-134) is the same network with a bias-free fc and a `backbone(x)`
 that stops at the pooled features: the model of the angular-margin supervised mode (MODEL.MARGIN).
 """
@@ -26,10 +30,10 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, dist
 from ._lib import call, ptr
-from .conformer import (BN_EPS_STEM, CONV_BF16, GRAD_SINKS, MAP_BF16, NativeConformer, _ConvHeadFn, _fl, _GradSink, _Map,
-                        _map_dtype, _MaxPoolFn, _join_queued, _own, _rup, _s, bn, bn_conv, conv)
+from .conformer import (BN_EPS_STEM, BN_MOMENTUM, CONV_BF16, GRAD_SINKS, MAP_BF16, NativeConformer, _ConvHeadFn, _fl,
+                        _GradSink, _Map, _map_dtype, _MaxPoolFn, _join_queued, _own, _rup, _s, bn, bn_conv, conv)
 
 BN_EPS = 1e-5  # timm BasicBlock norm_layer = nn.BatchNorm2d (default eps)
 
@@ -38,9 +42,12 @@ class ResNetConfig:
     """The default is timm's resnet18 (BasicBlocks); `RESNET50` below is its resnet50 (Bottlenecks)."""
 
     def __init__(self, layers=(2, 2, 2, 2), num_classes=23, img_size=224, widths=(64, 128, 256, 512), fc_bias=True,
-                 block="basic"):
+                 block="basic", se=False):
         if block not in ("basic", "bottleneck"):
             raise ValueError(f"block {block!r}: 'basic' or 'bottleneck'")
+        if se and block != "bottleneck":
+            raise ValueError("se=True: the squeeze-excite gate sits in a Bottleneck (code/models/se.py:8-58)")
+        self.se = bool(se)  # SEResNet's Bottleneck: conv_down / conv_up gate bn3's output (NativeSEResNet)
         self.layers, self.widths = tuple(layers), tuple(widths)
         self.num_classes, self.img_size = num_classes, img_size
         self.fc_bias = bool(fc_bias)  # False: ModelMargin's nn.Linear(num_features, C, bias=False)
@@ -83,6 +90,9 @@ def resnet_layout(cfg):
             out += [(pre + "conv1.weight", (w, inp, 1, 1), "p")] + _bn_entries(pre + "bn1.", w)
             out += [(pre + "conv2.weight", (w, w, 3, 3), "p")] + _bn_entries(pre + "bn2.", w)
             out += [(pre + "conv3.weight", (outp, w, 1, 1), "p")] + _bn_entries(pre + "bn3.", outp)
+            if getattr(cfg, "se", False):  # code/models/se.py:23-26, registered after bn3 and before downsample
+                out += [(pre + "conv_down.weight", (w // 4, outp, 1, 1), "p"),
+                        (pre + "conv_up.weight", (outp, w // 4, 1, 1), "p")]
         else:
             out += [(pre + "conv1.weight", (w, inp, 3, 3), "p")] + _bn_entries(pre + "bn1.", w)
             out += [(pre + "conv2.weight", (w, w, 3, 3), "p")] + _bn_entries(pre + "bn2.", w)
@@ -178,8 +188,12 @@ class NativeResNet(NativeConformer):
             sc = conv(self, x, _Map.nhwc(x), pre + "downsample.0.weight", None, outp, 1, stride, 0, stats=True,
                       sink=sink)
             sc = bn(self, sc, pre + "downsample.1.", eps=BN_EPS)
-            return bn(self, h, pre + "bn3.", eps=BN_EPS, relu=True, res=sc)
-        return bn(self, h, pre + "bn3.", eps=BN_EPS, relu=True, res=x, res_sink=sink)
+            return self._bottleneck_tail(h, pre, sc, None)
+        return self._bottleneck_tail(h, pre, x, sink)
+
+    def _bottleneck_tail(self, h, pre, res, res_sink):
+        """conv3's output -> the block's output: relu(bn3(h) + res)."""
+        return bn(self, h, pre + "bn3.", eps=BN_EPS, relu=True, res=res, res_sink=res_sink)
 
     def _block(self, x, pre, inp, planes, stride, ds):
         """timm BasicBlock.forward: relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut); Bottleneck: _bottleneck."""
@@ -320,3 +334,114 @@ class ModelMargin(NativeResNet):
                 continue
             own[k[len("model."):] if k.startswith("model.") else k] = v
         return super().load_state_dict(own, strict=strict)
+
+
+class _SETailFn(torch.autograd.Function):
+    """The tail of an SE-ResNet Bottleneck (code/models/se.py:43-58) after conv3, on csrc/se.hip:
+    out = relu(s * bn3(y) + res), s = sigmoid(conv_up(relu(conv_down(pool(bn3(y)))))), with bn3's output never
+    written -- its pool is bn3's affine map of y's per-image channel means (es_se_squeeze_ex, the one added read
+    of y), the gate is [N, C]-sized (es_se_gate_fwd) and the apply pass is BatchNorm's with the gate
+    (es_se_bn_apply_ex).  Statistics as bn(): from conv3's epilogue partials where it left them (train mode, bf16
+    convs, one rank), else from the library's channel sums; eval mode reads the running buffers.  Backward: one sums
+    pass (es_se_bn_bwd_sums_ex), the gate's backward with bn3's and both SE weights' gradients written to the flat
+    gradient (es_se_gate_bwd), one dx pass that also writes the shortcut's gradient (es_se_bn_bwd_dx_ex)."""
+
+    @staticmethod
+    def forward(ctx, y, res, m, pre, eps, res_sink=None):
+        y, res = y.contiguous(), res.contiguous()
+        if res.dtype != y.dtype or res.shape != y.shape:
+            raise _lib.EndosslCallError(f"{pre}: residual map {res.dtype} {tuple(res.shape)} vs conv3's "
+                                        f"{y.dtype} {tuple(y.shape)}")
+        N, H, W, C = y.shape
+        HW, rows = H * W, N * H * W
+        R = m.shapes[pre + "conv_down.weight"][0]
+        train = m.training
+        if train and getattr(m, "sync_bn", True) and dist.world_size() > 1:
+            raise NotImplementedError("the SE tail takes one rank's BatchNorm statistics: SyncBatchNorm over "
+                                      f"{dist.world_size()} ranks is not built for NativeSEResNet (eval mode works)")
+        lib, dev, fl = _lib.load(), y.device, _fl(y)
+        bnp = pre + "bn3."
+        gam, bet = m.pview(bnp + "weight"), m.pview(bnp + "bias")
+        rm, rv, nbt = m.bn_buffers(bnp)
+        mean, rstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
+        part = m._bn_partials.pop(y.data_ptr(), None) if train else None
+        if part is not None and part[1] == y.shape:
+            call("es_bn2d_fwd_partials_ex", ptr(y), rows, C, ptr(part[0]), ptr(gam), ptr(bet), ptr(rm), ptr(rv), ptr(nbt),
+                 BN_MOMENTUM, eps, None, 1, None, ptr(mean), ptr(rstd), fl, _s())
+        elif train:
+            sums = torch.empty(2, C, device=dev)
+            ws = torch.empty(lib.es_chan_workspace(rows, C), device=dev)
+            call("es_bn2d_sums_ex", ptr(y), rows, C, 0, None, 0, ptr(sums[0]), ptr(ws), fl, _s())
+            call("es_bn2d_sums_ex", ptr(y), rows, C, 1, ptr(sums[0]), rows, ptr(sums[1]), ptr(ws), fl, _s())
+            call("es_se_bn_stats", ptr(sums[0]), ptr(sums[1]), rows, C, eps, BN_MOMENTUM, 1, ptr(mean), ptr(rstd), ptr(rm),
+                 ptr(rv), ptr(nbt), _s())
+        else:
+            call("es_se_bn_stats", None, None, rows, C, eps, BN_MOMENTUM, 0, ptr(mean), ptr(rstd), ptr(rm), ptr(rv), None,
+                 _s())
+        ybar, a, s = (torch.empty(N, C, device=dev) for _ in range(3))
+        h = torch.empty(N, R, device=dev)
+        ws = torch.empty(lib.es_se_squeeze_workspace(N, HW, C, fl), device=dev)
+        call("es_se_squeeze_ex", ptr(y), N, HW, C, ptr(mean), ptr(rstd), ptr(gam), ptr(bet), ptr(ybar), ptr(a), ptr(ws),
+             fl, _s())
+        call("es_se_gate_fwd", ptr(a), ptr(m.pview(pre + "conv_down.weight")), ptr(m.pview(pre + "conv_up.weight")), N,
+             C, R, ptr(h), ptr(s), _s())
+        out = torch.empty_like(y)
+        call("es_se_bn_apply_ex", ptr(y), ptr(res), ptr(s), N, HW, C, ptr(mean), ptr(rstd), ptr(gam), ptr(bet), ptr(out),
+             fl, _s())
+        ctx.save_for_backward(y, out, mean, rstd, ybar, a, h, s)
+        ctx.m, ctx.pre, ctx.train, ctx.res_sink = m, pre, train, res_sink
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        _own(dout)
+        y, out, mean, rstd, ybar, a, h, s = ctx.saved_tensors
+        m, pre = ctx.m, ctx.pre
+        N, H, W, C = y.shape
+        HW, R = H * W, h.shape[1]
+        lib, dev, fl = _lib.load(), y.device, _fl(y)
+        dout = dout.contiguous()
+        if dout.dtype != y.dtype:
+            dout = dout.to(y.dtype)
+        bnp = pre + "bn3."
+        gam, bet = m.pview(bnp + "weight"), m.pview(bnp + "bias")
+        dgam, dbet = m.gview(bnp + "weight"), m.gview(bnp + "bias")
+        p1, p2, da = (torch.empty(N, C, device=dev) for _ in range(3))
+        ws = torch.empty(lib.es_se_bn_bwd_sums_workspace(N, HW, C, fl), device=dev)
+        call("es_se_bn_bwd_sums_ex", ptr(y), ptr(out), ptr(dout), N, HW, C, ptr(mean), ptr(rstd), ptr(p1), ptr(p2),
+             ptr(ws), fl, _s())
+        wsg = torch.empty(lib.es_se_gate_bwd_workspace(N, C, R), device=dev)
+        call("es_se_gate_bwd", ptr(p1), ptr(p2), ptr(ybar), ptr(a), ptr(h), ptr(s),
+             ptr(m.pview(pre + "conv_down.weight")), ptr(m.pview(pre + "conv_up.weight")), ptr(gam), ptr(bet), ptr(mean),
+             ptr(rstd), N, C, R, ptr(m.gview(pre + "conv_down.weight")), ptr(m.gview(pre + "conv_up.weight")), ptr(da),
+             ptr(dgam), ptr(dbet), ptr(wsg), _s())
+        # the shortcut's gradient: into the block input's _GradSink where the shortcut is the identity (this
+        # backward runs before conv1's, as bn3's does in NativeResNet: it is the sink's first writer)
+        sink = ctx.res_sink
+        gres, acc = sink.take(lambda: torch.empty_like(y)) if sink is not None else (torch.empty_like(y), 0)
+        dy = torch.empty_like(y)
+        call("es_se_bn_bwd_dx_ex", ptr(y), ptr(out), ptr(dout), ptr(s), ptr(da), N, HW, C, ptr(mean), ptr(rstd), ptr(gam),
+             ptr(dgam), ptr(dbet), 1 if ctx.train else 0, ptr(dy), ptr(gres), acc, fl, _s())
+        if sink is not None:
+            gres = sink.give(gres, acc)
+        return dy, gres, None, None, None, None
+
+
+class NativeSEResNet(NativeResNet):
+    """SE-ResNet-50, the reference's `resnet50se` (code/build.py:152-170: SEResNet(Bottleneck, [3, 4, 6, 3]),
+    code/models/se.py:8-119): ResNet-50 with a squeeze-excite gate on bn3's output in every Bottleneck.  The stem, the
+    stride on conv2, the downsample, the init rule and fc are NativeResNet's; only the block tail differs
+    (_SETailFn).  state_dict = the reference's (conv_down / conv_up after bn3.*, before downsample.*).
+
+    The pool before fc is the global one: the reference's nn.AvgPool2d(7) equals it at 224^2 (a 7 x 7 last map)
+    and fails or reads a corner at other sizes.  A train-mode forward on more than one rank raises
+    (the tail takes one rank's BatchNorm statistics); steps run eagerly (no graph replay)."""
+
+    def __init__(self, cfg=None, seed=None, **kw):
+        cfg = cfg if cfg is not None else ResNetConfig(se=True, **{**RESNET50, **kw})
+        if not getattr(cfg, "se", False):
+            raise ValueError("NativeSEResNet's blocks carry conv_down / conv_up: build its config with se=True")
+        super().__init__(cfg, seed=seed)
+
+    def _bottleneck_tail(self, h, pre, res, res_sink):
+        return _SETailFn.apply(h, res, self, pre, BN_EPS, res_sink)

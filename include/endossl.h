@@ -689,6 +689,52 @@ int es_ce_weighted_fwd_bwd_global(const float* logits, int ldl, const int64_t* t
                                   const float* wsum_global, int n, int C, float grad_scale, float* dlogits, int lddl,
                                   float* out, hipStream_t stream);
 
+/* ---- squeeze-excite bottleneck tail (code/models/se.py:32-58; csrc/se.hip) -------------------- */
+/* The tail of an SE-ResNet Bottleneck after conv3, with bn3's output o = gamma (y - mean) rstd + beta never
+ * written: a = pool(o) = gamma (pool(y) - mean) rstd + beta, h = relu(a W_down^T), s = sigmoid(h W_up^T),
+ * out = relu(s o + res).  y / res / out / dout / dy / gres are NHWC maps [N, HW, C], fp32 (flags 0) or bf16
+ * (flags bit 0); ybar, a, s, da, p1, p2 are fp32 [N, C]; h is fp32 [N, R]; w_down [R, C], w_up [C, R] fp32.
+ * Supported: C % 16 == 0, 16 <= C <= 2048, 1 <= R <= 128, N, HW >= 1 (else ES_BAD_SHAPE); maps and per-channel
+ * arrays 16-byte aligned, no null required pointer (else ES_BAD_ARG); both before any launch.  Every sum is taken
+ * in a fixed order (no atomics) and every output element is written. */
+/* mean / rstd for the tail where conv3's epilogue partials are not available.  train: from sum = es_bn2d_sums_ex
+ * mode 0 and sq = mode 1 over `rows` rows (biased variance; running buffers with the unbiased one,
+ * num_batches_tracked += 1 when non-null); eval (train 0): mean = running_mean, rstd = 1 / sqrt(running_var +
+ * eps), sum / sq unused */
+int es_se_bn_stats(const float* sum, const float* sq, int rows, int C, float eps, float momentum, int train,
+                   float* mean, float* rstd, float* running_mean, float* running_var, void* num_batches_tracked,
+                   hipStream_t stream);
+/* workspace sizes in floats (0 for an unsupported shape) */
+size_t es_se_squeeze_workspace(int N, int HW, int C, int flags);
+size_t es_se_bn_bwd_sums_workspace(int N, int HW, int C, int flags);
+size_t es_se_gate_bwd_workspace(int N, int C, int R);
+/* ybar[n][c] = mean_hw y (fp32 accumulation), a = gamma (ybar - mean) rstd + beta: one read of y */
+int es_se_squeeze_ex(const void* y, int N, int HW, int C, const float* mean, const float* rstd, const float* gamma,
+                     const float* beta, float* ybar, float* a, float* workspace, int flags, hipStream_t stream);
+int es_se_gate_fwd(const float* a, const float* w_down, const float* w_up, int N, int C, int R, float* h, float* s,
+                   hipStream_t stream);
+/* out = relu(s o + res) in es_bn2d_fwd_ex's affine form and rounding: with s == 1 bit-identical to
+ * es_bn2d_fwd_ex(res, relu = 1) on the same mean / rstd */
+int es_se_bn_apply_ex(const void* y, const void* res, const float* s, int N, int HW, int C, const float* mean,
+                      const float* rstd, const float* gamma, const float* beta, void* out, int flags,
+                      hipStream_t stream);
+/* g = dout [out > 0]; p1[n][c] = sum_hw g, p2[n][c] = sum_hw g xhat, xhat = (y - mean) rstd */
+int es_se_bn_bwd_sums_ex(const void* y, const void* out, const void* dout, int N, int HW, int C, const float* mean,
+                         const float* rstd, float* p1, float* p2, float* workspace, int flags, hipStream_t stream);
+/* dt = (gamma p2 + beta p1) s (1 - s); dw_up = dt^T h; dh = (dt W_up) [h > 0]; dw_down = dh^T a; da = dh W_down;
+ * dbeta = sum_n (s p1 + da); dgamma = sum_n (s p2 + da (ybar - mean) rstd): all overwritten */
+int es_se_gate_bwd(const float* p1, const float* p2, const float* ybar, const float* a, const float* h,
+                   const float* s, const float* w_down, const float* w_up, const float* gamma, const float* beta,
+                   const float* mean, const float* rstd, int N, int C, int R, float* dw_down, float* dw_up, float* da,
+                   float* dgamma, float* dbeta, float* workspace, hipStream_t stream);
+/* d_o = g s + da / HW; train: dy = gamma rstd (d_o - dbeta / M - xhat dgamma / M), M = N HW; eval (train 0):
+ * dy = gamma rstd d_o (dgamma / dbeta unused); gres (+)= g, the shortcut's gradient (accumulate: the second
+ * consumer of a gradient sink) */
+int es_se_bn_bwd_dx_ex(const void* y, const void* out, const void* dout, const float* s, const float* da, int N,
+                       int HW, int C, const float* mean, const float* rstd, const float* gamma, const float* dgamma,
+                       const float* dbeta, int train, void* dy, void* gres, int accumulate, int flags,
+                       hipStream_t stream);
+
 /* ---- optimizer / EMA (code/optimizer.py:50-51, code/ema.py:51-62) ----------------------------- */
 int es_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2,
                      float eps, float neg_step, float bc2_sqrt, float decay, float one_minus_decay,
