@@ -733,7 +733,7 @@ int es_dropout_keep(void* keep, long n, float p, unsigned long long seed, unsign
 
 int es_dense_fwd(const float* X, int ldx, const float* W, const float* b, float* Y, int ldy, int n, int K, int N,
                  int act, float slope, const void* keep, float keep_scale, hipStream_t stream) {
-  if (n <= 0 || K <= 0 || N <= 0 || K > 2048 || act < 0 || act > 2) return ES_BAD_SHAPE;
+  if (n <= 0 || K <= 0 || N <= 0 || K > 2048 || act < 0 || act > 2 || ldx < K || ldy < N) return ES_BAD_SHAPE;
   if (!X || !W || !Y) return ES_BAD_ARG;
   if (N < 64) {
     const long outs = (long)n * N;
@@ -756,6 +756,7 @@ int es_dense_bwd(const float* dY, int lddy, const float* Yact, int ldya, int act
                  float keep_scale, const float* X, int ldx, const float* W, float* dX, int lddx, int accumulate_dx,
                  float* dW, float* db, int n, int K, int N, float* workspace, hipStream_t stream) {
   if (n <= 0 || K <= 0 || N <= 0 || N > 2048 || act < 0 || act > 2) return ES_BAD_SHAPE;
+  if (lddy < N || ldx < K || (act && ldya < N) || (dX && lddx < K)) return ES_BAD_SHAPE;
   if (!dY || !X || !W || !dW || !workspace || (act && !Yact)) return ES_BAD_ARG;
   hipLaunchKernelGGL(dense_dpre_kernel, (n * N + 255) / 256, 256, 0, stream, dY, lddy, Yact, ldya, act, slope,
                      (const uint8_t*)keep, keep_scale, workspace, n, N);
@@ -775,7 +776,7 @@ int es_dense_bwd(const float* dY, int lddy, const float* Yact, int ldya, int act
 int es_bn1d_fwd(const float* U, int ldu, const float* gamma, const float* beta, float* running_mean, float* running_var,
                 void* num_batches_tracked, float momentum, float eps, int train, float* Y, int ldy, float* xhat,
                 float* rstd, int n, int F, hipStream_t stream) {
-  if (n <= 0 || F <= 0) return ES_BAD_SHAPE;
+  if (n <= 0 || F <= 0 || ldu < F || ldy < F) return ES_BAD_SHAPE;
   if (!U || !gamma || !beta || !running_mean || !running_var || !Y || (train && (!xhat || !rstd))) return ES_BAD_ARG;
   hipLaunchKernelGGL(bn1d_fwd_kernel, F, 256, 0, stream, U, ldu, gamma, beta, running_mean, running_var,
                      (long long*)num_batches_tracked, momentum, eps, train, Y, ldy, xhat, rstd, n, F);
@@ -784,7 +785,7 @@ int es_bn1d_fwd(const float* U, int ldu, const float* gamma, const float* beta, 
 
 int es_bn1d_bwd(const float* dY, int lddy, const float* xhat, const float* rstd, const float* gamma, float* dU,
                 int lddu, float* dgamma, float* dbeta, int n, int F, hipStream_t stream) {
-  if (n <= 0 || F <= 0) return ES_BAD_SHAPE;
+  if (n <= 0 || F <= 0 || lddy < F || lddu < F) return ES_BAD_SHAPE;
   if (!dY || !xhat || !rstd || !gamma || !dU || !dgamma || !dbeta) return ES_BAD_ARG;
   hipLaunchKernelGGL(bn1d_bwd_kernel, F, 256, 0, stream, dY, lddy, xhat, rstd, gamma, dU, lddu, dgamma, dbeta, n, F);
   return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
@@ -792,7 +793,7 @@ int es_bn1d_bwd(const float* dY, int lddy, const float* xhat, const float* rstd,
 
 // SyncBatchNorm1d (data-parallel CoMatch head), see the kernels above.  N = global row count.
 int es_bn1d_sums(const float* U, int ldu, int n, int F, const float* S1, float N, float* out, hipStream_t stream) {
-  if (n <= 0 || F <= 0 || N < (float)n) return ES_BAD_SHAPE;
+  if (n <= 0 || F <= 0 || N < (float)n || ldu < F) return ES_BAD_SHAPE;
   if (!U || !out) return ES_BAD_ARG;
   hipLaunchKernelGGL(bn1d_sums_kernel, F, 256, 0, stream, U, ldu, S1, N, out, n);
   return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
@@ -802,7 +803,7 @@ int es_bn1d_fwd_global(const float* U, int ldu, const float* gamma, const float*
                        const float* S2, float N, float* running_mean, float* running_var, void* num_batches_tracked,
                        float momentum, float eps, float* Y, int ldy, float* xhat, float* rstd, int n, int F,
                        hipStream_t stream) {
-  if (n <= 0 || F <= 0 || N < (float)n) return ES_BAD_SHAPE;
+  if (n <= 0 || F <= 0 || N < (float)n || ldu < F || ldy < F) return ES_BAD_SHAPE;
   if (!U || !gamma || !beta || !S1 || !S2 || !running_mean || !running_var || !Y || !xhat || !rstd) return ES_BAD_ARG;
   hipLaunchKernelGGL(bn1d_fwd_global_kernel, F, 256, 0, stream, U, ldu, gamma, beta, S1, S2, N, running_mean,
                      running_var, (long long*)num_batches_tracked, momentum, eps, Y, ldy, xhat, rstd, n, F);
@@ -810,7 +811,7 @@ int es_bn1d_fwd_global(const float* U, int ldu, const float* gamma, const float*
 }
 
 int es_bn1d_bwd_sums(const float* dY, int lddy, const float* xhat, int n, int F, float* out, hipStream_t stream) {
-  if (n <= 0 || F <= 0) return ES_BAD_SHAPE;
+  if (n <= 0 || F <= 0 || lddy < F) return ES_BAD_SHAPE;
   if (!dY || !xhat || !out) return ES_BAD_ARG;
   hipLaunchKernelGGL(bn1d_bwd_sums_kernel, F, 256, 0, stream, dY, lddy, xhat, out, n, F);
   return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
@@ -819,7 +820,7 @@ int es_bn1d_bwd_sums(const float* dY, int lddy, const float* xhat, int n, int F,
 int es_bn1d_bwd_global(const float* dY, int lddy, const float* xhat, const float* rstd, const float* gamma,
                        const float* sums_global, const float* sums_local, float N, float* dU, int lddu,
                        float* dgamma, float* dbeta, int n, int F, hipStream_t stream) {
-  if (n <= 0 || F <= 0 || N < (float)n) return ES_BAD_SHAPE;
+  if (n <= 0 || F <= 0 || N < (float)n || lddy < F || lddu < F) return ES_BAD_SHAPE;
   if (!dY || !xhat || !rstd || !gamma || !sums_global || !sums_local || !dU || !dgamma || !dbeta) return ES_BAD_ARG;
   hipLaunchKernelGGL(bn1d_bwd_global_kernel, F, 256, 0, stream, dY, lddy, xhat, rstd, gamma, sums_global, sums_local,
                      N, dU, lddu, dgamma, dbeta, n, F);
@@ -827,7 +828,7 @@ int es_bn1d_bwd_global(const float* dY, int lddy, const float* xhat, const float
 }
 
 int es_l2norm_fwd(const float* V, int ldv, float* Z, int ldz, float* norm, int n, int L, hipStream_t stream) {
-  if (n <= 0 || L <= 0) return ES_BAD_SHAPE;
+  if (n <= 0 || L <= 0 || ldv < L || ldz < L) return ES_BAD_SHAPE;
   if (!V || !Z || !norm) return ES_BAD_ARG;
   hipLaunchKernelGGL(l2norm_fwd_kernel, (n + 3) / 4, 256, 0, stream, V, ldv, Z, ldz, norm, n, L);
   return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
@@ -835,7 +836,7 @@ int es_l2norm_fwd(const float* V, int ldv, float* Z, int ldz, float* norm, int n
 
 int es_l2norm_bwd(const float* dZ, int lddz, const float* Z, int ldz, const float* norm, float* dV, int lddv, int n,
                   int L, hipStream_t stream) {
-  if (n <= 0 || L <= 0) return ES_BAD_SHAPE;
+  if (n <= 0 || L <= 0 || lddz < L || ldz < L || lddv < L) return ES_BAD_SHAPE;
   if (!dZ || !Z || !norm || !dV) return ES_BAD_ARG;
   hipLaunchKernelGGL(l2norm_bwd_kernel, (n + 3) / 4, 256, 0, stream, dZ, lddz, Z, ldz, norm, dV, lddv, n, L);
   return hipGetLastError() == hipSuccess ? ES_OK : ES_HIP_ERROR;
@@ -850,9 +851,7 @@ size_t es_comatch_pseudo_workspace(int nu, int C, int Q) {
 // across ranks, then handed to es_comatch_pseudo_ex with hist_given = 1)
 __global__ __launch_bounds__(256) void softmax_colmean_kernel(const float* __restrict__ lw, int ldl, int n, int C,
                                                               float* __restrict__ out) {
-  __shared__ float acc[32];
-  if (threadIdx.x < 32) acc[threadIdx.x] = 0.f;
-  __syncthreads();
+  __shared__ float red[256];
   float loc[32];
   for (int c = 0; c < C; ++c) loc[c] = 0.f;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
@@ -863,9 +862,11 @@ __global__ __launch_bounds__(256) void softmax_colmean_kernel(const float* __res
     for (int c = 0; c < C; ++c) s += expf(l[c] - mx);
     for (int c = 0; c < C; ++c) loc[c] += expf(l[c] - mx) / s;
   }
-  for (int c = 0; c < C; ++c) atomicAdd(&acc[c], loc[c]);
-  __syncthreads();
-  if (threadIdx.x < C) out[threadIdx.x] = acc[threadIdx.x] / n;
+  // a class at a time, the 256 partials in wg_sum256's fixed tree order: the same bits on every launch
+  for (int c = 0; c < C; ++c) {
+    const float s = wg_sum256(loc[c], red);
+    if (threadIdx.x == 0) out[c] = s / n;
+  }
 }
 
 int es_softmax_colmean(const float* logits, int ldl, int n, int C, float* out, hipStream_t stream) {
@@ -974,7 +975,7 @@ int es_comatch_contrastive_fwd_bwd_ex(const float* z0, int ldz0, const float* z1
 int es_comatch_focal_fwd_bwd(const float* ls, int ldl, const float* probs, const float* mask, int nu, int C,
                              float gamma, float grad_scale, float* loss_out, float* dls, int lddl, float* workspace,
                              hipStream_t stream) {
-  if (nu <= 0 || C <= 0) return ES_BAD_SHAPE;
+  if (nu <= 0 || C <= 0 || ldl < C || lddl < C) return ES_BAD_SHAPE;
   if (!ls || !probs || !mask || !loss_out || !dls || !workspace) return ES_BAD_ARG;
   hipLaunchKernelGGL(focal_kernel, (nu + 255) / 256, 256, 0, stream, ls, ldl, probs, mask, nu, C, gamma, grad_scale,
                      dls, lddl, workspace);

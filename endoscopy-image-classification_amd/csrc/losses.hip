@@ -32,6 +32,10 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return s;
 }
 
+// The class index of a 64-bit target, or -1 where the value itself lies outside [0, C): the range check comes
+// before the narrowing, so 2^32 + 3 is invalid and not class 3.
+__device__ __forceinline__ int target_index(int64_t y64, int C) { return y64 >= 0 && y64 < C ? (int)y64 : -1; }
+
 __global__ __launch_bounds__(256) void fm_consistency_kernel(const float* __restrict__ lw, int ldw,
                                                              const float* __restrict__ ls, int lds_, int n, int C,
                                                              float tau, float grad_scale, int* __restrict__ pl,
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(256) void poly_ce_kernel(const float* __restrict__ 
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += __expf(lr[c] - mx);
     const float lse = mx + __logf(se);
-    const int yi = (int)y[i];
+    const int yi = target_index(y[i], C);
     if ((unsigned)yi >= (unsigned)C) {  // invalid target: NaN loss, no gradient, no out-of-range read
       sum += __int_as_float(0x7fc00000);
       for (int c = 0; c < C; ++c) dl[(size_t)i * lddl + c] = 0.f;
@@ -128,7 +132,7 @@ __global__ __launch_bounds__(256) void ce_weighted_kernel(const float* __restric
   __shared__ float red[16];
   float ws = 0.f;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const int yi = (int)y[i];
+    const int yi = target_index(y[i], C);
     ws += (unsigned)yi >= (unsigned)C ? __int_as_float(0x7fc00000) : (w ? w[yi] : 1.f);
   }
   float W = block_sum(ws, red);
@@ -143,7 +147,7 @@ __global__ __launch_bounds__(256) void ce_weighted_kernel(const float* __restric
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += __expf(lr[c] - mx);
     const float lse = mx + __logf(se);
-    const int yi = (int)y[i];
+    const int yi = target_index(y[i], C);
     if ((unsigned)yi >= (unsigned)C) {  // invalid target: NaN loss (via the weight sum), no gradient
       for (int c = 0; c < C; ++c) dl[(size_t)i * lddl + c] = 0.f;
       continue;
@@ -165,7 +169,7 @@ __global__ __launch_bounds__(256) void ce_weight_sum_kernel(const int64_t* __res
   __shared__ float red[16];
   float ws = 0.f;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const int yi = (int)y[i];
+    const int yi = target_index(y[i], C);
     ws += (unsigned)yi >= (unsigned)C ? __int_as_float(0x7fc00000) : (w ? w[yi] : 1.f);
   }
   ws = block_sum(ws, red);
@@ -432,7 +436,7 @@ extern "C" {
 // out[0] = weighted-mean CE (weights nullable -> plain mean); dl = grad_scale * d(out[0])/d logits
 int es_ce_weighted_fwd_bwd(const float* logits, int ldl, const int64_t* targets, const float* weights, int n, int C,
                            float grad_scale, float* dlogits, int lddl, float* out, hipStream_t stream) {
-  if (n <= 0 || C <= 0) return ES_BAD_SHAPE;
+  if (n <= 0 || C <= 0 || ldl < C || lddl < C) return ES_BAD_SHAPE;
   if (!logits || !targets || !dlogits || !out) return ES_BAD_ARG;
   hipLaunchKernelGGL(ce_weighted_kernel, 1, 256, 0, stream, logits, ldl, targets, weights, nullptr, n, C, grad_scale,
                      dlogits, lddl, out);
@@ -453,7 +457,7 @@ int es_ce_weight_sum(const int64_t* targets, const float* weights, int n, int C,
 int es_ce_weighted_fwd_bwd_global(const float* logits, int ldl, const int64_t* targets, const float* weights,
                                   const float* wsum_global, int n, int C, float grad_scale, float* dlogits, int lddl,
                                   float* out, hipStream_t stream) {
-  if (n <= 0 || C <= 0) return ES_BAD_SHAPE;
+  if (n <= 0 || C <= 0 || ldl < C || lddl < C) return ES_BAD_SHAPE;
   if (!logits || !targets || !dlogits || !out || !wsum_global) return ES_BAD_ARG;
   hipLaunchKernelGGL(ce_weighted_kernel, 1, 256, 0, stream, logits, ldl, targets, weights, wsum_global, n, C,
                      grad_scale, dlogits, lddl, out);
@@ -465,7 +469,7 @@ int es_ce_weighted_fwd_bwd_global(const float* logits, int ldl, const int64_t* t
 int es_fm_consistency_fwd_bwd(const float* logits_w, int ldw, const float* logits_s, int lds, int n, int C,
                               float tau, float grad_scale, int* pseudo_label, uint8_t* mask, float* row_loss,
                               float* dlogits_s, int lddls, float* out, hipStream_t stream) {
-  if (n <= 0 || C <= 0 || C > MAXC) return ES_BAD_SHAPE;
+  if (n <= 0 || C <= 0 || C > MAXC || ldw < C || lds < C || lddls < C) return ES_BAD_SHAPE;
   if (!logits_w || !logits_s || !dlogits_s || !out) return ES_BAD_ARG;
   hipLaunchKernelGGL(fm_consistency_kernel, 1, 256, 0, stream, logits_w, ldw, logits_s, lds, n, C, tau, grad_scale,
                      pseudo_label, mask, row_loss, dlogits_s, lddls, out);
@@ -475,7 +479,7 @@ int es_fm_consistency_fwd_bwd(const float* logits_w, int ldw, const float* logit
 // out[0] = poly loss (mean over n); dl = grad_scale * n * d(loss)/d l  (grad_scale = 1/n for d loss)
 int es_poly_ce_fwd_bwd(const float* logits, int ldl, const int64_t* targets, const float* weights, int n, int C,
                        float epsilon, float grad_scale, float* dlogits, int lddl, float* out, hipStream_t stream) {
-  if (n <= 0 || C <= 0 || C > MAXC) return ES_BAD_SHAPE;
+  if (n <= 0 || C <= 0 || C > MAXC || ldl < C || lddl < C) return ES_BAD_SHAPE;
   if (!logits || !targets || !dlogits || !out) return ES_BAD_ARG;
   hipLaunchKernelGGL(poly_ce_kernel, 1, 256, 0, stream, logits, ldl, targets, weights, n, C, epsilon, grad_scale,
                      dlogits, lddl, out);

@@ -276,6 +276,8 @@ int es_cls_ln_bwd(const float* dfts, int lddf, const float* gamma, const float* 
                   int lddx, int T, float* dgamma, float* dbeta, int n, int D, hipStream_t stream);
 
 /* ---- CoMatch heads (fp32; code/models/custom_model.py:107-145,201-205) ------------------------- */
+/* Every leading dimension of a used operand must be at least its width (else ES_BAD_SHAPE, before any launch); the
+ * same holds for es_comatch_focal_fwd_bwd, es_fm_consistency_fwd_bwd, es_poly_ce_fwd_bwd and es_ce_weighted_*. */
 /* Y = act(X W^T + b) (* keep * keep_scale, the replayed Dropout keep-mask, uint8 [n, N]);
  * act 0 = none, 1 = ReLU, 2 = LeakyReLU(slope) */
 int es_dense_fwd(const float* X, int ldx, const float* W, const float* b, float* Y, int ldy, int n, int K, int N,
@@ -364,7 +366,9 @@ int es_comatch_focal_fwd_bwd(const float* ls, int ldl, const float* probs, const
 int es_fm_consistency_fwd_bwd(const float* logits_w, int ldw, const float* logits_s, int lds, int n, int C,
                               float tau, float grad_scale, int* pseudo_label, uint8_t* mask, float* row_loss,
                               float* dlogits_s, int lddls, float* out, hipStream_t stream);
-/* code/loss.py:103-114,308-364 ce_loss(type_loss='poly') = PolyLoss(epsilon=2); out[0]=loss */
+/* code/loss.py:103-114,308-364 ce_loss(type_loss='poly') = PolyLoss(epsilon=2); out[0]=loss.  A target outside
+ * [0, C) as a 64-bit value (2^32 + 3 is not class 3): NaN loss, zero gradient in that row, no out-of-range read;
+ * es_ce_weighted_* and es_ce_weight_sum check their targets the same way. */
 int es_poly_ce_fwd_bwd(const float* logits, int ldl, const int64_t* targets, const float* weights, int n, int C,
                        float epsilon, float grad_scale, float* dlogits, int lddl, float* out, hipStream_t stream);
 
