@@ -71,6 +71,10 @@ SIGNATURES = {
     "es_dense_fwd": (I, [V, I, V, V, V, I, I, I, I, I, F, V, F, V]),
     "es_dense_bwd_workspace": (Z, [I, I]),
     "es_dense_bwd": (I, [V, I, V, I, I, F, V, F, V, I, V, V, I, I, V, V, I, I, I, V, V]),
+    "es_dense_wide_tile": (I, [I]),
+    "es_dense_wide_fwd": (I, [V, I, V, V, V, I, I, I, I, I, F, V, F, V]),
+    "es_dense_wide_bwd_workspace": (Z, [I, I, I, I]),
+    "es_dense_wide_bwd": (I, [V, I, V, I, I, F, V, F, V, I, V, V, I, I, V, V, I, I, I, V, V]),
     "es_bn1d_fwd": (I, [V, I, V, V, V, V, V, F, F, I, V, I, V, V, I, I, V]),
     "es_bn1d_bwd": (I, [V, I, V, V, V, V, I, V, V, I, I, V]),
     "es_dropout_keep": (I, [V, L, F, U64, U64, V]),

@@ -17,16 +17,21 @@ reads; a margin with any other backbone raises (ModelMargin needs `.fc`) unless 
 trainer tests first and which keeps building the plain backbone.
 `resnet18` and `resnet50` (the backbone ten of the reference's eighteen configs name) give resnet.NativeResNet with
 timm's state_dict -- for FixMatch and for the plain supervised mode.  The modes that wrap the backbone in ModelwEmb
-(CoMatch, IS_TRIPLET without SSL, EZBM) need an embedding head over a CNN trunk, which is not built: they raise for
-the ResNets instead of returning a logits-only model.  `resnet50se` (code/build.py:152-170, the reference's own
+(CoMatch, IS_TRIPLET without SSL, EZBM) get comatch_model.NativeResNetEmb -- ModelwEmb over the native ResNet trunk,
+LOW_DIM-d under CoMatch and 256-d otherwise, MODEL.PRE_TRAIN_PATH (the 2-class abnormality checkpoint) loaded into the
+trunk -- when asked to: build_model(config, cnn_emb=True), or ENDOSSL_CNN_EMB=1 for a script that calls
+build_model(config).  Without the switch they raise for resnet50 instead of returning a logits-only model (and
+resnet18 keeps its logits-only model), as before NativeResNetEmb existed.  `resnet50se` (code/build.py:152-170, the reference's own
 SEResNet, code/models/se.py) gives resnet.NativeSEResNet for FixMatch and the plain supervised mode, with the 2-class
 abnormality checkpoint of MODEL.PRE_TRAIN_PATH re-headed as the reference does; IS_TRIPLET, CoMatch and MARGIN raise
 for it.  Other CNN / Swin backbones are outside the hot path
 (SURVEY.md §2 rows 6, 18).
 """
+import os
+
 import torch
 
-from .comatch_model import NativeViTEmb
+from .comatch_model import NativeResNetEmb, NativeViTEmb
 from .conformer import ConformerConfig, NativeConformer
 from .resnet import RESNET50, ModelMargin, NativeResNet, NativeSEResNet, ResNetConfig
 from .vit import VIT_CONFIGS, NativeViT, ViTConfig
@@ -61,7 +66,34 @@ def _build_resnet50se(config, C, seed):
     return model
 
 
-def build_model(config, is_pathology=True, seed=0):
+def _emb_mode(config):
+    """The mode that wraps the backbone in ModelwEmb (code/build.py:175-178,198-200), or None: (message text,
+    low_dim).  CoMatch reads MODEL.LOW_DIM; the triplet branch passes none, so ModelwEmb's default holds."""
+    ssl = bool(getattr(getattr(config, "TRAIN", None), "IS_SSL", True))  # a config without TRAIN: the SSL default
+    if ssl and getattr(config.MODEL, "TYPE_SEMI", "FixMatch") == "CoMatch":
+        return "TYPE_SEMI 'CoMatch'", int(getattr(config.MODEL, "LOW_DIM", 64))
+    if not ssl and getattr(config.MODEL, "IS_TRIPLET", False):
+        return "IS_TRIPLET without IS_SSL (the triplet mode, EZBM)", TRIPLET_LOW_DIM
+    return None
+
+
+def _build_resnet_emb(config, name, C, low_dim, seed):
+    """ModelwEmb over the native ResNet trunk.  MODEL.PRE_TRAIN_PATH: the 2-class abnormality checkpoint into the
+    trunk (code/models/custom_model.py:180-190: its own fc dropped, the heads freshly initialised)."""
+    model = NativeResNetEmb(ResNetConfig(num_classes=C, head="emb", low_dim=low_dim, **RESNETS[name]), seed=seed)
+    path = getattr(config.MODEL, "PRE_TRAIN_PATH", "None")
+    if path not in (None, "None", ""):
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        model.load_trunk(ck["model_state_dict"])
+    return model
+
+
+def build_model(config, is_pathology=True, seed=0, cnn_emb=None):
+    """cnn_emb: build ModelwEmb over resnet18 / resnet50 (comatch_model.NativeResNetEmb) for the modes that need it;
+    None reads ENDOSSL_CNN_EMB (default "0": those modes keep raising for resnet50, and resnet18 keeps its
+    logits-only model)."""
+    if cnn_emb is None:
+        cnn_emb = os.environ.get("ENDOSSL_CNN_EMB", "0") == "1"
     name = config.MODEL.NAME
     C = int(config.MODEL.NUM_CLASSES)
     if name == "resnet50se":
@@ -92,17 +124,17 @@ def build_model(config, is_pathology=True, seed=0):
         # the supervised baseline (BASELINE configs[0]; code/build.py:218-220 timm.create_model('resnet18',
         # num_classes=C): ImageNet weights are a download, unavailable here -- timm's random init) and resnet50,
         # FixMatch's (code/build.py:196-197) and the supervised mode's backbone in most reference configs
-        if name != "resnet18":
-            # code/build.py:175-178,198-200 wrap the backbone in ModelwEmb (logits, fts, z) -- checked before
-            # PRE_TRAIN_PATH there too; the triplet step and both EZBM stages read fts / z
-            ssl = bool(getattr(config.TRAIN, "IS_SSL", True))
-            mode = ("TYPE_SEMI 'CoMatch'" if ssl and getattr(config.MODEL, "TYPE_SEMI", "FixMatch") == "CoMatch" else
-                    "IS_TRIPLET without IS_SSL (the triplet mode, EZBM)"
-                    if not ssl and getattr(config.MODEL, "IS_TRIPLET", False) else None)
-            if mode is not None:
-                raise NotImplementedError(f"{name} for {mode}: ModelwEmb (code/models/custom_model.py:136-213) over "
-                                          "a CNN trunk is not built -- the native embedding-head models are the "
-                                          f"ViTs; {name} is native for FixMatch, plain supervised and MODEL.MARGIN")
+        # code/build.py:175-178,198-200 wrap the backbone in ModelwEmb (logits, fts, z) -- checked before
+        # PRE_TRAIN_PATH there too; the triplet step and both EZBM stages read fts / z
+        mode = _emb_mode(config)
+        if mode is not None and cnn_emb:
+            return _build_resnet_emb(config, name, C, mode[1], seed)
+        if mode is not None and name != "resnet18":
+            raise NotImplementedError(f"{name} for {mode[0]}: ModelwEmb (code/models/custom_model.py:136-213) over "
+                                      "a CNN trunk is not built by default -- the native embedding-head models are "
+                                      f"the ViTs; {name} is native for FixMatch, plain supervised and MODEL.MARGIN.  "
+                                      "build_model(config, cnn_emb=True) or ENDOSSL_CNN_EMB=1 builds "
+                                      "NativeResNetEmb, ModelwEmb over the native ResNet trunk")
         if getattr(config.MODEL, "PRE_TRAIN_PATH", "None") not in (None, "None", ""):
             raise NotImplementedError(f"{name} + PRE_TRAIN_PATH swaps fc for build_head's MLP "
                                       "(code/build.py:202-211): outside the native scope")

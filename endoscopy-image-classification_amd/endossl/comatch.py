@@ -53,6 +53,9 @@ class CoMatch(FixMatch):
         return [self.model.fc, self.model.head_emb]
 
     def get_config(self, config):
+        if dist.world_size() > 1 and getattr(self.model, "cnn_emb", False):
+            raise NotImplementedError("CoMatch over NativeResNetEmb runs in one process: the contrastive graph and "
+                                      "the SyncBatchNorm1d head over a SyncBatchNorm trunk are untested data-parallel")
         super().get_config(config)
         dev = self.model.flat.device
         self.low_dim = config.MODEL.LOW_DIM

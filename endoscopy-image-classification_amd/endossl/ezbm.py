@@ -240,8 +240,8 @@ class EZBM(SupLearning):
         N = self._bank_n
         s = _lib.stream()
         W = self._stage2_workspace(n)
-        heads, eng = m.heads(), m.engine()
-        view, gview = (lambda nm: eng.view(m.flat, nm)), (lambda nm: eng.view(m.flat_grad, nm))
+        heads = m.heads()
+        view, gview = m.head_views()
         if idx is not None:
             idx_in = idx.to(dev, torch.int32).contiguous()
             dual_in = dual.to(dev, torch.int32).contiguous()

@@ -34,6 +34,7 @@ from . import _lib, dist
 from ._lib import call, ptr
 from .conformer import (BN_EPS_STEM, BN_MOMENTUM, CONV_BF16, GRAD_SINKS, MAP_BF16, NativeConformer, _ConvHeadFn, _fl,
                         _GradSink, _Map, _map_dtype, _MaxPoolFn, _join_queued, _own, _rup, _s, bn, bn_conv, conv)
+from .vit import emb_head_layout
 
 BN_EPS = 1e-5  # timm BasicBlock norm_layer = nn.BatchNorm2d (default eps)
 
@@ -42,9 +43,15 @@ class ResNetConfig:
     """The default is timm's resnet18 (BasicBlocks); `RESNET50` below is its resnet50 (Bottlenecks)."""
 
     def __init__(self, layers=(2, 2, 2, 2), num_classes=23, img_size=224, widths=(64, 128, 256, 512), fc_bias=True,
-                 block="basic", se=False):
+                 block="basic", se=False, head="cls", low_dim=64):
         if block not in ("basic", "bottleneck"):
             raise ValueError(f"block {block!r}: 'basic' or 'bottleneck'")
+        if head not in ("cls", "emb"):
+            raise ValueError(f"head {head!r}: 'cls' (timm's fc) or 'emb' (ModelwEmb's fc / head_emb)")
+        if head == "emb" and (se or not fc_bias):
+            raise ValueError("head='emb': ModelwEmb's heads over the plain ResNet trunk (no se, no bias-free fc)")
+        # "emb": ModelwEmb's heads on the pooled features (comatch_model.NativeResNetEmb), low_dim = L
+        self.head, self.low_dim = head, int(low_dim)
         if se and block != "bottleneck":
             raise ValueError("se=True: the squeeze-excite gate sits in a Bottleneck (code/models/se.py:8-58)")
         self.se = bool(se)  # SEResNet's Bottleneck: conv_down / conv_up gate bn3's output (NativeSEResNet)
@@ -58,6 +65,11 @@ class ResNetConfig:
     def num_features(self):
         """Channels of the last stage = the pooled feature width = fc's fan-in (512 | 2048)."""
         return self.widths[-1] * self.expansion
+
+    @property
+    def dim(self):
+        """The feature width under the name the embedding heads and the trainers read (ViTConfig.dim)."""
+        return self.num_features
 
     def blocks(self):
         """(prefix, inplanes, planes, stride, downsample) per block in state_dict order; a block's output has
@@ -98,6 +110,14 @@ def resnet_layout(cfg):
             out += [(pre + "conv2.weight", (w, w, 3, 3), "p")] + _bn_entries(pre + "bn2.", w)
         if ds:
             out += [(pre + "downsample.0.weight", (outp, inp, 1, 1), "p")] + _bn_entries(pre + "downsample.1.", outp)
+    if getattr(cfg, "head", "cls") == "emb":
+        # ModelwEmb: timm's fc replaced by the complex head, head_emb after it; fc.3 is a BatchNorm1d whose running
+        # buffers ride the same flat-parameter plumbing as the trunk's BatchNorm2d buffers
+        for name, shape in emb_head_layout(cfg):
+            out.append((name, shape, "p"))
+            if name == "fc.3.bias":
+                out += _bn_entries("fc.3.", shape[0])[2:]
+        return out
     C = cfg.num_classes
     out += [("fc.weight", (C, cfg.widths[-1] * getattr(cfg, "expansion", 1)), "p")]
     if getattr(cfg, "fc_bias", True):
@@ -109,12 +129,23 @@ def init_resnet_(flat, layout, offs, generator=None):
     """timm ResNet.init_weights: kaiming-normal (fan_out, ReLU) convs, BatchNorm weight 1 / bias 0,
     fc as nn.Linear's default (uniform +-1/sqrt(fan_in) for weight and bias).  Every BatchNorm weight is 1, a
     block's last one (bn2 / bn3) included: timm's zero_init_last_bn is not restated."""
-    fan_in = next(shape[1] for name, shape, _ in layout if name == "fc.weight")
+    fan_in = next((shape[1] for name, shape, _ in layout if name == "fc.weight"), None)
+    shapes = {name: shape for name, shape, _ in layout}
     for name, shape, kind in layout:
         if kind != "p":
             continue
         t = flat[offs[name]:offs[name] + math.prod(shape)].view(shape)
-        if len(shape) == 4:
+        if fan_in is None and name.startswith(("fc.", "head_emb.")):
+            # ModelwEmb's heads keep the PyTorch defaults, as NativeViTEmb's (vit.timm_init_): Linear
+            # kaiming_uniform(a=sqrt(5)) with bias U(+-1/sqrt(fan_in)), BatchNorm1d weight 1 / bias 0
+            if name.startswith("fc.3."):
+                t.fill_(1.0 if name.endswith("weight") else 0.0)
+            elif len(shape) == 2:
+                nn.init.kaiming_uniform_(t, a=math.sqrt(5), generator=generator)
+            else:
+                bound = 1.0 / math.sqrt(shapes[name[:-len("bias")] + "weight"][1])
+                nn.init.uniform_(t, -bound, bound, generator=generator)
+        elif len(shape) == 4:
             std = math.sqrt(2.0 / (shape[0] * shape[2] * shape[3]))
             t.normal_(0.0, std, generator=generator)
         elif name.startswith("fc."):

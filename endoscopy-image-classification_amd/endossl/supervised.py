@@ -86,6 +86,9 @@ class SupLearning(Trainer):
         if self.is_triplet and not emb:
             raise ValueError("MODEL.IS_TRIPLET needs the embedding-head model (logits, fts, z): build it with "
                              "build_model(config) with MODEL.IS_TRIPLET set and TRAIN.IS_SSL off")
+        if self.is_triplet and dist.world_size() > 1 and getattr(self.model, "cnn_emb", False):
+            raise NotImplementedError("the triplet step over NativeResNetEmb runs in one process: the SyncBatchNorm1d "
+                                      "head over a SyncBatchNorm trunk is untested data-parallel")
         self.triplet_alpha = 0.7  # TripletLoss(alpha=0.7) (code/supervised.py:60)
         self.triplet_dist = {"d_ap": [], "d_an": []}
         self._tws = {}

@@ -287,6 +287,21 @@ size_t es_dense_bwd_workspace(int n, int N);
 int es_dense_bwd(const float* dY, int lddy, const float* Yact, int ldya, int act, float slope, const void* keep,
                  float keep_scale, const float* X, int ldx, const float* W, float* dX, int lddx, int accumulate_dx,
                  float* dW, float* db, int n, int K, int N, float* workspace, hipStream_t stream);
+/* The same two layers as tiled fp32 GEMMs on the exact f32-input MFMA (csrc/dense_wide.hip), for the heads over a wide
+ * trunk (ResNet-50: D = 2048): arguments and semantics of es_dense_fwd / es_dense_bwd, K and N up to 4096 and n up to
+ * 65535 * 32 rows (the row tiles are one grid dimension; more is ES_BAD_SHAPE, a workspace of 0 floats), results
+ * bit-identical from run to run (split reductions go through the workspace and are added in a fixed order; no
+ * atomics).  The workspace holds dpre [n, N] and the split partials of dW and, with want_dx, of dX.
+ * es_dense_wide_tile(0 / 1 / 2 / 3): the kernels' row tile, column tile, reduction step and the workgroup count the
+ * backward splits its reductions towards (what the tile-edge tests derive their shapes from). */
+int es_dense_wide_tile(int which);
+int es_dense_wide_fwd(const float* X, int ldx, const float* W, const float* b, float* Y, int ldy, int n, int K, int N,
+                      int act, float slope, const void* keep, float keep_scale, hipStream_t stream);
+size_t es_dense_wide_bwd_workspace(int n, int K, int N, int want_dx);
+int es_dense_wide_bwd(const float* dY, int lddy, const float* Yact, int ldya, int act, float slope, const void* keep,
+                      float keep_scale, const float* X, int ldx, const float* W, float* dX, int lddx,
+                      int accumulate_dx, float* dW, float* db, int n, int K, int N, float* workspace,
+                      hipStream_t stream);
 /* BatchNorm1d (nn.BatchNorm1d semantics): train = batch statistics + running-buffer update
  * (momentum, unbiased variance, num_batches_tracked int64 += 1), eval = running statistics */
 int es_bn1d_fwd(const float* U, int ldu, const float* gamma, const float* beta, float* running_mean, float* running_var,

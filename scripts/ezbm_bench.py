@@ -3,7 +3,11 @@
 (the trainer's _finish_step alone, on the same trainer): the two alternated sample by sample in one process (device
 events around `--iters` back-to-back calls per sample, `--rounds` samples each after a warm-up), median / p10 /
 p90.  The bank lives on the device (random features, every class present); the trunk is never run.
-  python scripts/ezbm_bench.py [--rounds 40] [--iters 10] [--out profiles/ezbm_stage2.txt]"""
+  python scripts/ezbm_bench.py [--rounds 40] [--iters 10] [--out profiles/ezbm_stage2.txt]
+--model resnet50 times the published config's backbone instead (NativeResNetEmb, build_model's cnn_emb opt-in: D = 2048,
+F = 512, n = 192): --heads narrow | wide | both selects the head kernel family (comatch.hip's es_dense_* / the tiled
+es_dense_wide_* of EmbHeads.WIDE_LAYERS); `both` alternates the two on the one trainer, sample by sample.
+  python scripts/ezbm_bench.py --model resnet50 --heads both --out profiles/ezbm_stage2_resnet50.txt"""
 import argparse
 import os
 import sys
@@ -38,14 +42,14 @@ class _DL(list):
     dataset = _DS()
 
 
-def _trainer(bs, mu, expansion):
+def _trainer(bs, mu, expansion, model="vit_small_patch16_224"):
     cfg = AttrDict(DATA=AttrDict(BATCH_SIZE=bs, MU=mu, IMG_SIZE=224, TARGET_NAME="target"),
-                   MODEL=AttrDict(NAME="vit_small_patch16_224", NUM_CLASSES=len(CLS_NUM), MARGIN="None", IS_TRIPLET=True,
+                   MODEL=AttrDict(NAME=model, NUM_CLASSES=len(CLS_NUM), MARGIN="None", IS_TRIPLET=True,
                                   PRE_TRAIN_PATH="None"),
                    TRAIN=AttrDict(IS_SSL=False, USE_EMA=True, EMA_DECAY=0.999, BASE_LR=1e-3, CLS_WEIGHT=False,
                                   THRES=0.95, LAMBDA_C=4, EPOCHS=1, WARMUP_EPOCHS=0, DECAY_EPOCHS=10, WARMUP_LR=5e-4,
                                   LR_DECAY=0.8, SCH_NAME="const", FREQ_EVAL=1, EXPANSION=expansion))
-    tr = EZBM(build_model(cfg, seed=0), opt_func="Adam", lr=1e-3, device="cuda")
+    tr = EZBM(build_model(cfg, seed=0, cnn_emb=model.startswith("resnet")), opt_func="Adam", lr=1e-3, device="cuda")
     tr.get_dataloader(_DL(), None)
     tr.get_config(cfg)
     return tr
@@ -60,18 +64,29 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--model", default="vit_small_patch16_224", choices=["vit_small_patch16_224", "resnet50"])
+    ap.add_argument("--heads", default="both", choices=["narrow", "wide", "both"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ezbm_bench.py times steps on the MI355X: no GPU here, nothing measured")
-    tr = _trainer(args.bs, args.mu, args.expansion)
+    tr = _trainer(args.bs, args.mu, args.expansion, args.model)
     n, D, C = args.bs * args.mu, tr.model.cfg.dim, len(CLS_NUM)
     g = torch.Generator().manual_seed(0)
     N = sum(CLS_NUM)
     y = torch.cat([torch.full((c,), i, dtype=torch.int64) for i, c in enumerate(CLS_NUM)])[torch.randperm(N, generator=g)]
     tr.set_bank(torch.randn(N, D, generator=g).cuda(), y.cuda())
     tr.setup_stage_2()
-    calls = {f"stage-2 step ({n} rows, 2 x {n} through fc)": lambda: tr.step_stage_2(n=n),
-             "optimizer + EMA sweep alone (_finish_step)": lambda: (tr._inflight.wait(), tr._finish_step())}
+    def step(wide=None):
+        if wide is not None:
+            tr.model.wide_heads = wide
+        return tr.step_stage_2(n=n)
+
+    if args.model == "resnet50":
+        fams = {"narrow": (False,), "wide": (True,), "both": (False, True)}[args.heads]
+        calls = {f"stage-2 step ({n} rows), heads {'wide' if w else 'narrow'}": (lambda w=w: step(w)) for w in fams}
+    else:
+        calls = {f"stage-2 step ({n} rows, 2 x {n} through fc)": step}
+    calls["optimizer + EMA sweep alone (_finish_step)"] = lambda: (tr._inflight.wait(), tr._finish_step())
     for _ in range(args.warmup):
         for f in calls.values():
             f()
@@ -88,14 +103,14 @@ def main():
             times[k].append(e0.elapsed_time(e1) / args.iters * 1e3)  # us per call
     out = tr.step_stage_2(n=n)
     assert torch.isfinite(out["loss"]).item()
-    lines = [f"EZBM stage 2 at ViT-S/16's head: D = {D}, F = {D // 4}, C = {C}, n = {n} rows a step, bank of {N} rows, "
+    lines = [f"EZBM stage 2 at {'ViT-S/16' if args.model != 'resnet50' else 'ResNet-50'}'s head: D = {D}, F = {D // 4}, C = {C}, n = {n} rows a step, bank of {N} rows, "
              f"EXPANSION '{args.expansion}', Adam + EMA over the flat buffer of {tr.model.flat.numel()} floats; "
              f"{args.rounds} samples x {args.iters} calls each, alternated in one process; device events around "
              f"back-to-back calls (host launch gaps included)",
              f"{'call':<48}{'median us':>11}{'p10 us':>9}{'p90 us':>9}"]
     for k in calls:
         lines.append(f"{k:<48}{_pct(times[k], 0.5):>11.1f}{_pct(times[k], 0.1):>9.1f}{_pct(times[k], 0.9):>9.1f}")
-    a, b = (_pct(times[k], 0.5) for k in calls)
+    a, b = (_pct(times[k], 0.5) for k in (list(calls)[0], list(calls)[-1]))
     lines.append(f"sweep median / step median = {b / a:.3f}; step - sweep = {a - b:.1f} us for the sampler, the head's "
                  f"forward and backward over {2 * n} rows and the loss")
     text = "\n".join(lines)
