@@ -186,6 +186,21 @@ SIGNATURES = {
     "es_se_bn_bwd_sums_ex": (I, [V, V, V, I, I, I, V, V, V, V, V, I, V]),
     "es_se_gate_bwd": (I, [V, V, V, V, V, V, V, V, V, V, V, V, I, I, I, V, V, V, V, V, V, V]),
     "es_se_bn_bwd_dx_ex": (I, [V, V, V, V, V, I, I, I, V, V, V, V, V, I, V, V, I, I, V]),
+    # DenseNet: in-place dense blocks over one strided buffer (csrc/densenet.hip)
+    "es_conv2d_pack_bf16_pad": (I, [V, I, I, I, I, I, I, V, V, V]),
+    "es_conv_pack_pad_entry_size": (I, []),
+    "es_conv2d_pack_bf16_pad_multi": (I, [V, I, L, V]),
+    "es_dw_unpad_entry_size": (I, []),
+    "es_dw_unpad_multi": (I, [V, I, L, V]),
+    "es_bn2d_stats_ld_ex": (I, [V, I, I, L, F, V, V, V, V, I, V]),
+    "es_bn2d_stats_from_partials": (I, [V, I, I, I, F, V, V, V, V]),
+    "es_bn_running_entry_size": (I, []),
+    "es_bn2d_running_multi": (I, [V, I, I, V, V, I, F, V]),
+    "es_bn2d_eval_stats": (I, [V, V, I, I, F, V, V, V]),
+    "es_bn2d_apply_ld_ex": (I, [V, L, I, I, V, V, V, V, I, V, L, I, V]),
+    "es_bn2d_bwd_recompute_ld_ex": (I, [V, L, V, L, I, I, V, V, V, V, V, L, V, V, I, V, I, V]),
+    "es_avgpool2_ld_fwd_ex": (I, [V, I, I, I, I, V, L, I, V]),
+    "es_avgpool2_ld_bwd_ex": (I, [V, L, I, I, I, I, V, I, V]),
     "es_adam_ema_step": (I, [V, V, V, V, V, L, F, F, F, F, F, F, F, F, V]),
     "es_adamw_ema_step": (I, [V, V, V, V, V, V, L, F, F, F, F, F, F, F, F, F, F, F, F, F, V]),
     "es_sgd_ema_step": (I, [V, V, V, V, V, L, F, F, F, F, F, I, F, F, F, V]),

@@ -24,8 +24,10 @@ build_model(config).  Without the switch they raise for resnet50 instead of retu
 resnet18 keeps its logits-only model), as before NativeResNetEmb existed.  `resnet50se` (code/build.py:152-170, the reference's own
 SEResNet, code/models/se.py) gives resnet.NativeSEResNet for FixMatch and the plain supervised mode, with the 2-class
 abnormality checkpoint of MODEL.PRE_TRAIN_PATH re-headed as the reference does; IS_TRIPLET, CoMatch and MARGIN raise
-for it.  Other CNN / Swin backbones are outside the hot path
-(SURVEY.md §2 rows 6, 18).
+for it.  `densenet161` (three configs, `local_semisupervised.yaml` among them) gives densenet.NativeDenseNet with
+torchvision's state_dict for FixMatch and the plain supervised mode, MODEL.PRE_TRAIN_PATH re-headed the same way
+(`classifier.*` dropped when its class count differs); CoMatch, IS_TRIPLET without SSL and MARGIN raise for it.
+Other CNN / Swin backbones are outside the hot path.
 """
 import os
 
@@ -33,6 +35,7 @@ import torch
 
 from .comatch_model import NativeResNetEmb, NativeViTEmb
 from .conformer import ConformerConfig, NativeConformer
+from .densenet import DENSENET161, DenseNetConfig, NativeDenseNet
 from .resnet import RESNET50, ModelMargin, NativeResNet, NativeSEResNet, ResNetConfig
 from .vit import VIT_CONFIGS, NativeViT, ViTConfig
 
@@ -88,6 +91,30 @@ def _build_resnet_emb(config, name, C, low_dim, seed):
     return model
 
 
+def _build_densenet161(config, C, seed):
+    """code/build.py:196-197,218-220: timm.create_model('densenet161', num_classes=C) -> NativeDenseNet, for FixMatch
+    and the plain supervised mode.  The modes that need more than logits from the backbone raise."""
+    if str(getattr(config.MODEL, "MARGIN", "None")) != "None":  # code/build.py:173-174, checked first there
+        raise NotImplementedError("MODEL.MARGIN with backbone 'densenet161': ModelMargin needs a backbone with a .fc "
+                                  "classifier (code/models/custom_model.py:129) and timm's densenet161 has "
+                                  "`classifier`; the native ModelMargin backbones are resnet18 and resnet50")
+    mode = _emb_mode(config)
+    if mode is not None:
+        raise NotImplementedError(f"densenet161 for {mode[0]}: ModelwEmb (code/models/custom_model.py:136-213) over "
+                                  "the DenseNet trunk is not built -- densenet161 is native for FixMatch and plain "
+                                  "supervised")
+    model = NativeDenseNet(DenseNetConfig(num_classes=C, **DENSENET161), seed=seed)
+    path = getattr(config.MODEL, "PRE_TRAIN_PATH", "None")
+    if path not in (None, "None", ""):
+        # code/build.py:190-193,213-216: the 2-class abnormality checkpoint, re-headed (build_head: a plain Linear)
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        sd = ck.get("model_state_dict", ck)
+        if sd.get("classifier.weight") is not None and sd["classifier.weight"].shape[0] != C:
+            sd = {k: v for k, v in sd.items() if not k.startswith("classifier.")}
+        model.load_state_dict(sd, strict=False)
+    return model
+
+
 def build_model(config, is_pathology=True, seed=0, cnn_emb=None):
     """cnn_emb: build ModelwEmb over resnet18 / resnet50 (comatch_model.NativeResNetEmb) for the modes that need it;
     None reads ENDOSSL_CNN_EMB (default "0": those modes keep raising for resnet50, and resnet18 keeps its
@@ -98,6 +125,8 @@ def build_model(config, is_pathology=True, seed=0, cnn_emb=None):
     C = int(config.MODEL.NUM_CLASSES)
     if name == "resnet50se":
         return _build_resnet50se(config, C, seed)
+    if name == "densenet161":
+        return _build_densenet161(config, C, seed)
     if name != "conformer" and str(getattr(config.MODEL, "MARGIN", "None")) != "None":
         # code/build.py:173-174: checked before IS_SSL / IS_TRIPLET / PRE_TRAIN_PATH, none of which is read here
         if name in RESNETS:

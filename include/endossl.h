@@ -754,6 +754,69 @@ int es_se_bn_bwd_dx_ex(const void* y, const void* out, const void* dout, const f
                        const float* dbeta, int train, void* dy, void* gres, int accumulate, int flags,
                        hipStream_t stream);
 
+/* ---- DenseNet: dense blocks in place over one NHWC buffer (csrc/densenet.hip) ---------------------------------
+ * timm / torchvision `densenet161` (code/build.py:196-197,218-220; _DenseLayer: norm1 -> relu -> conv1 1x1 -> norm2
+ * -> relu -> conv2 3x3, the output concatenated after the input; _Transition: norm -> relu -> conv 1x1 ->
+ * AvgPool2d(2, 2)).  A block is one buffer [rows, ld]: layer i reads the channel prefix [0, C_i) and writes its
+ * growth slice through the convs' strides, so torch.cat and every later BatchNorm's statistics pass over the same
+ * channels disappear.  These replace aten cat / batch_norm / avg_pool2d around the convs above.
+ *
+ * Padded weight images: fp32 w [Cout][Cin][kh][kw] -> wp [Cout_p][kh kw][Cin_p], wt [Cin_p][kh kw][Cout_p] (bf16,
+ * either nullable), es_conv2d_pack_bf16's mapping and rounding with zeros in the padding; Cout_p, Cin_p % 8 == 0.
+ * _multi: n device-resident entries of es_conv_pack_pad_entry_size() bytes {const float* w; void* wp; void* wt;
+ * int Cout, Cin, kh_x_kw, Cout_p, Cin_p, 0}, max_elems = the largest Cout_p Cin_p kh kw. */
+int es_conv2d_pack_bf16_pad(const float* w, int Cout, int Cin, int kh, int kw, int Cout_p, int Cin_p, void* wp, void* wt,
+                            hipStream_t stream);
+int es_conv_pack_pad_entry_size(void);
+int es_conv2d_pack_bf16_pad_multi(const void* table, int n, long max_elems, hipStream_t stream);
+/* Padded weight gradients -> the true tensors: n device-resident entries of es_dw_unpad_entry_size() bytes
+ * {const float* src; float* dst; int Cout_p, Cin_p, Cout, Cin, kh_x_kw, 0}; dst [Cout][Cin][kh kw] (overwritten) = the
+ * true rows / columns of src [Cout_p][Cin_p][kh kw]; max_elems = the largest Cout Cin kh kw.  The entries are not
+ * validated (the caller checks them); rows are copied 16 bytes at a time where src and dst are 16-byte aligned and
+ * Cin kh kw % 4 == 0, element by element otherwise.  The _pad_multi pack likewise trusts its entries: wp / wt
+ * 16-byte aligned, Cout_p, Cin_p % 8 == 0, as es_conv2d_pack_bf16_pad checks for one weight. */
+int es_dw_unpad_entry_size(void);
+int es_dw_unpad_multi(const void* table, int n, long max_elems, hipStream_t stream);
+/* Batch statistics of the row-strided view x[r * ld + c] (r < rows, c < C <= ld): mean, rstd = 1 / sqrt(biased var +
+ * eps), m2 = the centred square sum.  es_bn2d_fwd_ex's statistics passes: the same bits on a contiguous copy.
+ * workspace: es_chan_workspace(rows, C) floats.  flags bit 0: x is bf16. */
+int es_bn2d_stats_ld_ex(const void* x, int rows, int C, long ld, float eps, float* mean, float* rstd, float* m2,
+                        float* workspace, int flags, hipStream_t stream);
+/* The same arrays from a bf16 conv's bn_partials (es_conv2d_bnstats_size(rows, PC) floats; PC = the conv's output
+ * channels, the first C taken): es_bn2d_fwd_partials_ex's combination bit for bit, no running-buffer update.  The
+ * partials are overwritten. */
+int es_bn2d_stats_from_partials(float* partials, int rows, int C, int PC, float eps, float* mean, float* rstd, float* m2,
+                                hipStream_t stream);
+/* Train-mode running-buffer update of n BatchNorms over one statistics array: n device-resident entries of
+ * es_bn_running_entry_size() bytes {float* running_mean; float* running_var; int64* num_batches_tracked; int C;
+ * int offset}, entry j reading mean / m2 [offset, offset + C).  Blend with momentum and the unbiased variance
+ * m2 / (rows - 1), num_batches_tracked += 1: es_bn2d_fwd_ex's update.  max_c = the largest C. */
+int es_bn_running_entry_size(void);
+int es_bn2d_running_multi(const void* table, int n, int max_c, const float* mean, const float* m2, int rows,
+                          float momentum, hipStream_t stream);
+/* Eval mode: mean[c] = running_mean[c], rstd[c] = 1 / sqrt(running_var[c] + eps) for c < C, zeros over [C, Cp) */
+int es_bn2d_eval_stats(const float* running_mean, const float* running_var, int C, int Cp, float eps, float* mean,
+                       float* rstd, hipStream_t stream);
+/* y[r * ldy + c] = bn(x[r * ldx + c]) (ReLU if relu) with the given mean / rstd: es_bn2d_fwd_ex's affine map and
+ * rounding.  flags bit 0: x is bf16, bit 1: y is bf16. */
+int es_bn2d_apply_ld_ex(const void* x, long ldx, int rows, int C, const float* mean, const float* rstd,
+                        const float* gamma, const float* beta, int relu, void* y, long ldy, int flags,
+                        hipStream_t stream);
+/* es_bn2d_bwd_recompute_ex between row-strided views x[r * ldx + c], dy[r * ldy + c], dx[r * lddx + c], c < C (columns
+ * beyond C untouched).  flags bit 0: x and dy are bf16; bit 1: dx is fp32 whatever the maps are; bit 2: dx
+ * accumulates (in fp32).  The dense kernel's reduction order: on contiguous views the same dx / dgamma / dbeta bits.
+ * workspace: es_chan_workspace(rows, C) floats. */
+int es_bn2d_bwd_recompute_ld_ex(const void* x, long ldx, const void* dy, long ldy, int rows, int C, const float* gamma,
+                                const float* beta, const float* mean, const float* rstd, void* dx, long lddx,
+                                float* dgamma, float* dbeta, int accumulate, float* workspace, int flags,
+                                hipStream_t stream);
+/* AvgPool2d(2, 2) of the dense map x [N, H, W, C] into the row-strided view y[((n Ho + ho) Wo + wo) * ldy + c], and
+ * its backward from a row-strided dy into the dense dx (overwritten).  es_avgpool2d_*_ex's values.  flags bit 0: the
+ * input (x / dy) is bf16, bit 1: the output (y / dx) is bf16. */
+int es_avgpool2_ld_fwd_ex(const void* x, int N, int H, int W, int C, void* y, long ldy, int flags, hipStream_t stream);
+int es_avgpool2_ld_bwd_ex(const void* dy, long lddy, int N, int H, int W, int C, void* dx, int flags,
+                          hipStream_t stream);
+
 /* ---- optimizer / EMA (code/optimizer.py:50-51, code/ema.py:51-62) ----------------------------- */
 int es_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2,
                      float eps, float neg_step, float bc2_sqrt, float decay, float one_minus_decay,
